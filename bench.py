@@ -23,6 +23,11 @@ N>1 the driver launches via torch.distributed.run with one rank per GPU.
 W untimed warmup steps, then EXACTLY K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; elapsed = MAX over ranks;
 rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print.
+``--dump-outputs DIR`` additionally saves the last timed step's results
+(inputs are seeded, so two builds can be compared array for array);
+``--full`` is where any measurement beyond the headline figure belongs.
 """
 from __future__ import annotations
 
@@ -73,7 +78,51 @@ def parse_args():
                    help="retain every ingested batch in the capacity-managed "
                         "HBM line buffer (BASELINE config 5) during the run")
     p.add_argument("--device", default=None)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's "
+                        "per-line results (rank 0) as DIR/<name>.npy, float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements that are not part of the "
+                        "headline figure (currently none: a plain run already "
+                        "does only setup, warmup, the timed steps and the "
+                        "result line)")
     return p.parse_args()
+
+
+#: --dump-outputs budget; larger results are row-sampled with a fixed seed
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir: str) -> None:
+    """Write what one step returned to its caller as DIR/<name>.npy.
+
+    ``outs`` is the step's list of process_packed() result dicts in line
+    order (one per ingested chunk); they are concatenated back into
+    whole-batch [B, ...] arrays: event_id, anomaly, scores, nv_unseen and
+    the parser's match tensors as match_<key>. Everything is stored as
+    float32 (ids, offsets and flags are far below 2^24, so exact). When
+    the batch would exceed DUMP_MAX_BYTES the same seeded row sample is
+    taken from every array and its indices saved as sample_rows.npy."""
+    import numpy as np
+
+    flat = []
+    for o in outs:
+        d = {k: o[k] for k in ("event_id", "anomaly", "scores", "nv_unseen")}
+        d.update({f"match_{k}": v for k, v in (o["match"] or {}).items()})
+        flat.append({k: v for k, v in d.items() if torch.is_tensor(v)})
+    arrays = {k: torch.cat([d[k] for d in flat]).to("cpu", torch.float32)
+              for k in flat[0]}
+    n_rows = int(arrays["event_id"].shape[0])
+    row_bytes = 4 * (1 + sum(a[0].numel() for a in arrays.values())) if n_rows else 0
+    if n_rows * row_bytes > DUMP_MAX_BYTES:
+        g = torch.Generator().manual_seed(0)
+        rows = torch.randperm(n_rows, generator=g)[: DUMP_MAX_BYTES // row_bytes]
+        rows = rows.sort().values
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.to(torch.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.contiguous().numpy())
 
 
 class ShardFeeder(threading.Thread):
@@ -271,7 +320,7 @@ def main() -> None:
         for r in readers:
             r.start()
 
-        def step(i: int) -> None:
+        def step(i: int) -> list:
             outs = []
             for q in queues:
                 while True:
@@ -299,6 +348,7 @@ def main() -> None:
                     sum(o["scores"].sum() for o in outs),
                 ]).to(device)
                 dmx_dist.all_gather_summaries(summary)
+            return outs
 
         def cleanup():
             for _, path in rings:
@@ -314,7 +364,7 @@ def main() -> None:
             lines, lens = ops.pack_lines(raw, args.max_len, device="cpu")
             pool_dev.append((lines.to(device), lens.to(device)))
 
-        def step(i: int) -> None:
+        def step(i: int) -> list:
             lines, lens = pool_dev[i % len(pool_dev)]
             if line_buf is not None:
                 line_buf.append(lines, lens)
@@ -329,6 +379,7 @@ def main() -> None:
                     [out["anomaly"].sum().float(), out["scores"].sum()]
                 ).to(device)
                 dmx_dist.all_gather_summaries(summary)
+            return [out]
 
         def cleanup():
             pass
@@ -367,10 +418,11 @@ def main() -> None:
 
     # ---- timed region: EXACTLY args.steps steps ----
     step_times = []
+    last_outs = []  # what the final timed step returned (--dump-outputs)
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        step(args.warmup + i)
+        last_outs = step(args.warmup + i)
         sync()
         step_times.append(time.perf_counter() - ts)
     sync()
@@ -384,6 +436,9 @@ def main() -> None:
         elapsed = float(e.item())
 
     cleanup()
+
+    if args.dump_outputs and rank == 0 and last_outs:
+        dump_outputs(last_outs, args.dump_outputs)
 
     total_lines = args.batch * args.steps * world_size
     lines_per_sec = total_lines / elapsed

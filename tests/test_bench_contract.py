@@ -39,6 +39,42 @@ def test_bench_single_process_contract():
     assert "model" in cfg and "global_batch" in cfg and "parallelism" in cfg
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32
+    .npy arrays, identical from run to run (seeded inputs); --full is
+    accepted and leaves the result line's meaning alone."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = subprocess.run(
+            [sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup",
+             "1", "--batch", "300", "--pool", "3", "--chunk", "64",
+             "--no-transformer", "--dump-outputs", str(tmp_path / name), *extra],
+            capture_output=True, text=True, timeout=300, cwd=ROOT,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = _last_json(out.stdout)
+        assert REQUIRED.issubset(d.keys())
+        assert d["metric"] == "lines_per_sec" and d["steps"] == 2
+        files = sorted((tmp_path / name).glob("*.npy"))
+        dumps.append({f.name: np.load(f) for f in files})
+    a, b = dumps
+    assert {"event_id.npy", "anomaly.npy", "scores.npy",
+            "nv_unseen.npy"}.issubset(a.keys())
+    assert a.keys() == b.keys()
+    total = 0
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape[0] == 300, k
+        assert np.array_equal(a[k], b[k]), k
+        total += a[k].nbytes
+    assert total <= 64 << 20
+    # the step after training on batch 0 sees fresh lines: parsed, and
+    # the NewValue probe really ran (not an all-zero placeholder)
+    assert (a["event_id.npy"] > 0).any()
+    assert a["nv_unseen.npy"].shape == (300, 3)
+
+
 @pytest.mark.timeout(400)
 def test_bench_torchrun_two_ranks_contract():
     """The driver's multi-rank launch shape (gloo over 127.0.0.1 here)."""
