@@ -14,6 +14,7 @@ Random-init weights (no network for checkpoints — BASELINE.md).
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 from typing import Dict, Optional
@@ -36,6 +37,15 @@ class BertTinyConfig:
     @property
     def head_dim(self) -> int:
         return self.hidden // self.heads
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_layout(n_layers: int) -> dict:
+    """Geometry, blob sizes and named offsets of the fused kernel, as the
+    extension compiled them (ops/csrc/kernels.h). Read-only."""
+    from ..ops import _dmx_C  # type: ignore[attr-defined]
+
+    return _dmx_C.bert_fused_layout(n_layers)
 
 
 class BertTinyDetectorModel:
@@ -137,21 +147,30 @@ class BertTinyDetectorModel:
     # ------------------------------------------------------------------
     # fused whole-model kernel path (ops/csrc/bert_fused.hip)
     # ------------------------------------------------------------------
+    def _fused_layout(self) -> dict:
+        return _fused_layout(self.config.layers)
+
+    def _fused_geometry_ok(self) -> bool:
+        """True when the config is the fixed geometry the fused kernel was
+        compiled for (any layer count)."""
+        lay = self._fused_layout()
+        return all(
+            getattr(self.config, k) == lay[k]
+            for k in ("hidden", "heads", "head_dim", "ffn", "max_seq", "vocab_size")
+        )
+
     def _fused_ok(self) -> bool:
-        c = self.config
         return (
             self.device.type == "cuda"
             and ops.have_extension()
-            and c.hidden == 128
-            and c.heads == 2
-            and c.ffn == 512
-            and c.max_seq == 64
-            and c.vocab_size == 259
+            and self._fused_geometry_ok()
         )
 
     def _fused_blobs(self):
-        """Pack weights into the (bf16, f32) blobs the fused kernel indexes
-        (layout MUST match bert_fused.hip WB_*/FB_* offsets)."""
+        """Pack weights into the (bf16, f32) blobs the fused kernel indexes:
+        tok_emb | pos_emb | per-layer weights | w_score, and per-layer
+        biases | b_score. The sizes are checked against the extension's
+        layout; tests/test_kernel_contracts.py checks the named offsets."""
         if getattr(self, "_wb", None) is None:
             parts = [self.tok_emb, self.pos_emb]
             for layer in self.layers:
@@ -160,12 +179,16 @@ class BertTinyDetectorModel:
                     layer["ln1_g"], layer["ln1_b"], layer["ln2_g"], layer["ln2_b"],
                 ]
             parts.append(self.w_score.reshape(-1))
-            self._wb = torch.cat([p.reshape(-1) for p in parts]).contiguous()
+            wb = torch.cat([p.reshape(-1) for p in parts]).contiguous()
             fparts = []
             for layer in self.layers:
                 fparts += [layer["bqkv"], layer["bo"], layer["b1"], layer["b2"]]
             fparts.append(self.b_score)
-            self._fb = torch.cat([p.reshape(-1) for p in fparts]).contiguous()
+            fb = torch.cat([p.reshape(-1) for p in fparts]).contiguous()
+            lay = self._fused_layout()
+            assert wb.numel() == lay["wb_elems"], (wb.numel(), lay["wb_elems"])
+            assert fb.numel() == lay["fb_elems"], (fb.numel(), lay["fb_elems"])
+            self._wb, self._fb = wb, fb
         return self._wb, self._fb
 
     def score_spans(

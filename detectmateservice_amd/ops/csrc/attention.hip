@@ -13,6 +13,7 @@
 // the linears carry the MFMA load). K staged row-major; scores read K rows
 // per-lane from LDS as bf16x8 vectors.
 #include "common.h"
+#include "kernels.h"
 
 #define ATTN_WAVES 4
 
@@ -93,10 +94,9 @@ void dmx_attention_bf16(
 }
 
 extern "C" void dmx_launch_attention_bf16(
-    const void* Q, const void* K, const void* V, void* O,
+    const int16_t* Q, const int16_t* K, const int16_t* V, int16_t* O,
     int BH, int S, int Dh, float scale, hipStream_t stream) {
   const size_t lds = (size_t)2 * S * Dh * sizeof(short);
   hipLaunchKernelGGL(dmx_attention_bf16, dim3(BH), dim3(ATTN_WAVES * DMX_WAVE),
-                     lds, stream, (const short*)Q, (const short*)K,
-                     (const short*)V, (short*)O, BH, S, Dh, scale);
+                     lds, stream, Q, K, V, O, BH, S, Dh, scale);
 }

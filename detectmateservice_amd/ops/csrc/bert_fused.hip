@@ -24,6 +24,7 @@
 // Fixed geometry (asserted host-side): S=64 tokens, H=128, 2 heads
 // (Dh=64), FFN=512, arbitrary layer count.
 #include "common.h"
+#include "kernels.h"  // geometry, blob offsets, BF_LDS_BYTES, launchers
 
 // Explicit LDS address-space typing: the noinline block_gemm receives the
 // arena pointers as arguments, and a generic (flat) short* there makes
@@ -35,12 +36,7 @@ typedef __attribute__((address_space(1))) const float glob_cfloat;
 typedef __attribute__((address_space(3))) const short lds_cshort;
 typedef __attribute__((address_space(3))) float lds_float;
 
-#define BF_WAVES 8
 #define BF_THREADS (BF_WAVES * DMX_WAVE)
-#define BF_S 64
-#define BF_H 128
-#define BF_DH 64
-#define BF_FFN 512
 
 // LDS strides (elements); +8 pads keep rows 16-B aligned and bank-spread
 #define XS (BF_H + 8)       // 136, x rows
@@ -57,25 +53,11 @@ typedef __attribute__((address_space(3))) float lds_float;
 #define O_OFF (BF_WAVES * 16 * VTS)    // 9216: attn-out after the P tiles
 #define BUF_ELEMS (O_OFF + BF_S * XS)  // 17920 = P+O (>= QK 17408)
 
-// bf16 weight-blob element offsets (host packs identically: bert_tiny.py)
-#define WB_TOK 0
-#define WB_POS (WB_TOK + 259 * BF_H)
-#define WB_LAYER0 (WB_POS + BF_S * BF_H)
-#define LW_QKV 0
-#define LW_WO (LW_QKV + 3 * BF_H * BF_H)
-#define LW_W1 (LW_WO + BF_H * BF_H)
-#define LW_W2 (LW_W1 + BF_FFN * BF_H)
-#define LW_LN1G (LW_W2 + BF_H * BF_FFN)
-#define LW_LN1B (LW_LN1G + BF_H)
-#define LW_LN2G (LW_LN1B + BF_H)
-#define LW_LN2B (LW_LN2G + BF_H)
-#define LW_SIZE (LW_LN2B + BF_H)
-// f32 blob: per layer [bqkv 384 | bo 128 | b1 512 | b2 128], then b_score
-#define FB_BQKV 0
-#define FB_BO (FB_BQKV + 3 * BF_H)
-#define FB_B1 (FB_BO + BF_H)
-#define FB_B2 (FB_B1 + BF_FFN)
-#define FB_SIZE (FB_B2 + BF_H)
+// arena: x [S][XS] | buf | Vt [2*Dh][VTS] (bf16), then [H] f32 pooling
+static_assert(BF_LDS_BYTES ==
+                  (BF_S * XS + BUF_ELEMS + 2 * BF_DH * VTS) * sizeof(short) +
+                      BF_H * sizeof(float),
+              "kernels.h BF_LDS_BYTES out of step with the LDS strides");
 
 // ---- in-block GEMM: out = act(in_lds[64][K] @ Wt[N][WTS] + bias) ---------
 // MODE 0: write out_lds[m][n]; MODE 1 (qkv): n<2H -> out (Q|K), else vt
@@ -233,7 +215,7 @@ static __device__ __forceinline__ void block_layernorm(
 // Per-wave phase timing (diagnostic builds): stamps[k] = s_memrealtime at
 // phase boundaries; slot pairs (work-done, barrier-crossed) separate each
 // wave's compute time from its barrier wait. 100 MHz constant clock.
-#define BF_NSTAMP 22
+// BF_NSTAMP slots per wave (kernels.h).
 
 template <int PHASES, bool TIMED = false, int ABL = 0>
 static __device__ __forceinline__ void bert_fused_body(
@@ -486,80 +468,98 @@ void dmx_bert_fused_timed(const unsigned char* lines, const int* start,
                                 max_len, n_layers, eps, stamps);
 }
 
-extern "C" void dmx_launch_bert_fused_timed(
-    const void* lines, const void* start, const void* end, const void* wb,
-    const void* fb, void* scores, void* stamps, int B, int max_len,
+// ---- host side -------------------------------------------------------------
+// The one launch path of all three entry points. BF_LDS_BYTES is above the
+// default dynamic-LDS limit, so each (kernel, device) pair needs the opt-in
+// attribute once; `attr_done` is that kernel's per-device flag array, which
+// keeps the attribute call off the production kernel's per-launch path
+// (unsynchronised on purpose: a racing second call sets the same value).
+constexpr int BF_MAX_DEVICES = 64;
+
+template <typename... KArgs, typename... Args>
+static hipError_t launch_bert_fused(void (*kernel)(KArgs...),
+                                    bool (&attr_done)[BF_MAX_DEVICES], int B,
+                                    hipStream_t stream, Args... args) {
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  if (dev < 0 || dev >= BF_MAX_DEVICES) return hipErrorInvalidDevice;
+  if (!attr_done[dev]) {
+    err = hipFuncSetAttribute((const void*)kernel,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              BF_LDS_BYTES);
+    if (err != hipSuccess) return err;
+    attr_done[dev] = true;
+  }
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(BF_THREADS), BF_LDS_BYTES, stream,
+                     args...);
+  return hipSuccess;  // launch errors surface through hipGetLastError()
+}
+
+extern "C" hipError_t dmx_launch_bert_fused_bf16(
+    const uint8_t* lines, const int32_t* start, const int32_t* end,
+    const int16_t* wb, const float* fb, float* scores, int B, int max_len,
     int n_layers, float eps, hipStream_t stream) {
-  const size_t lds =
-      ((size_t)BF_S * XS + BUF_ELEMS + (size_t)2 * BF_DH * VTS) *
-          sizeof(short) +
-      128 * sizeof(float);
-  hipFuncSetAttribute((const void*)dmx_bert_fused_timed,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(dmx_bert_fused_timed, dim3(B), dim3(BF_THREADS), lds,
-                     stream, (const unsigned char*)lines, (const int*)start,
-                     (const int*)end, (const short*)wb, (const float*)fb,
-                     (float*)scores, B, max_len, n_layers, eps,
-                     (unsigned long long*)stamps);
+  static bool attr_done[BF_MAX_DEVICES];
+  return launch_bert_fused(dmx_bert_fused_bf16, attr_done, B, stream, lines,
+                           start, end, wb, fb, scores, B, max_len, n_layers,
+                           eps);
 }
 
-extern "C" void dmx_launch_bert_fused_probe(
-    const void* lines, const void* start, const void* end, const void* wb,
-    const void* fb, void* scores, int B, int max_len, int n_layers,
-    float eps, int phase_mask, hipStream_t stream) {
-  const size_t lds =
-      ((size_t)BF_S * XS + BUF_ELEMS + (size_t)2 * BF_DH * VTS) *
-          sizeof(short) +
-      128 * sizeof(float);
-#define LAUNCH_PROBE(PH, AB)                                                 \
-  case ((PH) | ((AB) << 8)):                                                 \
-    hipFuncSetAttribute((const void*)dmx_bert_fused_probe<PH, AB>,           \
-                        hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                        (int)lds);                                           \
-    hipLaunchKernelGGL((dmx_bert_fused_probe<PH, AB>), dim3(B),              \
-                       dim3(BF_THREADS), lds, stream,                        \
-                       (const unsigned char*)lines, (const int*)start,       \
-                       (const int*)end, (const short*)wb, (const float*)fb,  \
-                       (float*)scores, B, max_len, n_layers, eps);           \
-    break;
+extern "C" hipError_t dmx_launch_bert_fused_timed(
+    const uint8_t* lines, const int32_t* start, const int32_t* end,
+    const int16_t* wb, const float* fb, float* scores, int64_t* stamps, int B,
+    int max_len, int n_layers, float eps, hipStream_t stream) {
+  static bool attr_done[BF_MAX_DEVICES];
+  return launch_bert_fused(dmx_bert_fused_timed, attr_done, B, stream, lines,
+                           start, end, wb, fb, scores, B, max_len, n_layers,
+                           eps, (unsigned long long*)stamps);
+}
+
+// Compiled probe variants as X(phases, ablation); phase_mask = PH | AB << 8.
+#define BF_PROBE_VARIANTS(X)                                                 \
+  X(0, 0)                                                                    \
+  X(PH_QKV, 0)                                                               \
+  X(PH_QKV | PH_ATTN, 0)                                                     \
+  X(PH_QKV | PH_ATTN | PH_PROJ, 0)                                           \
+  X(PH_QKV | PH_ATTN | PH_PROJ | PH_LN, 0)                                   \
+  X(PH_ALL, 0)                                                               \
+  X(PH_FFN, 0)                                                               \
+  X(PH_LN, 0)                                                                \
+  /* perf-ablation variants (numerically wrong by design): */                \
+  X(PH_ALL, 1) /* B operand constant (no L2 weight loads) */                 \
+  X(PH_ALL, 2) /* A operand constant (no LDS activation reads) */            \
+  X(PH_ALL, 3) /* both constant (pure MFMA + epilogue) */                    \
+  X(PH_FFN, 1)                                                               \
+  X(PH_FFN, 2)                                                               \
+  X(PH_FFN, 3)
+
+extern "C" bool dmx_bert_fused_probe_mask_known(int phase_mask) {
   switch (phase_mask) {
-    LAUNCH_PROBE(0, 0)
-    LAUNCH_PROBE(PH_QKV, 0)
-    LAUNCH_PROBE(PH_QKV | PH_ATTN, 0)
-    LAUNCH_PROBE(PH_QKV | PH_ATTN | PH_PROJ, 0)
-    LAUNCH_PROBE(PH_QKV | PH_ATTN | PH_PROJ | PH_LN, 0)
-    LAUNCH_PROBE(PH_ALL, 0)
-    LAUNCH_PROBE(PH_FFN, 0)
-    LAUNCH_PROBE(PH_LN, 0)
-    // perf-ablation variants (numerically wrong by design):
-    LAUNCH_PROBE(PH_ALL, 1)   // B operand constant (no L2 weight loads)
-    LAUNCH_PROBE(PH_ALL, 2)   // A operand constant (no LDS activation reads)
-    LAUNCH_PROBE(PH_ALL, 3)   // both constant (pure MFMA + epilogue)
-    LAUNCH_PROBE(PH_FFN, 1)
-    LAUNCH_PROBE(PH_FFN, 2)
-    LAUNCH_PROBE(PH_FFN, 3)
+#define KNOWN(PH, AB) case ((PH) | ((AB) << 8)):
+    BF_PROBE_VARIANTS(KNOWN)
+#undef KNOWN
+    return true;
     default:
-      break;
+      return false;
   }
-#undef LAUNCH_PROBE
 }
 
-extern "C" void dmx_launch_bert_fused_bf16(
-    const void* lines, const void* start, const void* end, const void* wb,
-    const void* fb, void* scores, int B, int max_len, int n_layers, float eps,
-    hipStream_t stream) {
-  const size_t lds =
-      ((size_t)BF_S * XS + BUF_ELEMS + (size_t)2 * BF_DH * VTS) *
-          sizeof(short) +
-      128 * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)dmx_bert_fused_bf16,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
+extern "C" hipError_t dmx_launch_bert_fused_probe(
+    const uint8_t* lines, const int32_t* start, const int32_t* end,
+    const int16_t* wb, const float* fb, float* scores, int B, int max_len,
+    int n_layers, float eps, int phase_mask, hipStream_t stream) {
+  switch (phase_mask) {
+#define LAUNCH_PROBE(PH, AB)                                                 \
+  case ((PH) | ((AB) << 8)): {                                               \
+    static bool attr_done[BF_MAX_DEVICES];                                   \
+    return launch_bert_fused(dmx_bert_fused_probe<PH, AB>, attr_done, B,     \
+                             stream, lines, start, end, wb, fb, scores, B,   \
+                             max_len, n_layers, eps);                        \
   }
-  hipLaunchKernelGGL(dmx_bert_fused_bf16, dim3(B), dim3(BF_THREADS), lds,
-                     stream, (const unsigned char*)lines, (const int*)start,
-                     (const int*)end, (const short*)wb, (const float*)fb,
-                     (float*)scores, B, max_len, n_layers, eps);
+    BF_PROBE_VARIANTS(LAUNCH_PROBE)
+#undef LAUNCH_PROBE
+    default:
+      return hipErrorInvalidValue;
+  }
 }

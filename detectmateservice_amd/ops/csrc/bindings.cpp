@@ -1,106 +1,147 @@
 // Torch extension bindings for the detectmate-mi355x HIP kernels.
 //
-// All entry points validate shapes/dtypes/contiguity, run on the CURRENT
-// torch HIP stream, and are gfx950-only (no CPU fallback here — the Python
-// layer in detectmateservice_amd/ops/__init__.py owns the CPU path and
-// fails loudly when this extension is missing on a GPU box).
+// All entry points validate every tensor they pass down (dtype, rank,
+// contiguity, shape relations, one common GPU), run on the current torch
+// HIP stream of the tensors' device, read the launch result, and are
+// gfx950-only (no CPU fallback here — the Python layer in
+// detectmateservice_amd/ops/__init__.py owns the CPU path and fails loudly
+// when this extension is missing on a GPU box).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
+#include <c10/hip/HIPException.h>
 
 #include <cstdint>
+#include <initializer_list>
 
-extern "C" {
-void dmx_launch_fused_linear_bf16(const void*, const void*, const void*,
-                                  void*, int, int, int, int, hipStream_t);
-void dmx_launch_probe_mfma(const void*, const void*, void*, int, int,
-                           hipStream_t);
-void dmx_launch_probe_mfma32(const void*, const void*, void*, hipStream_t);
-void dmx_launch_layernorm_bf16(const void*, const void*, const void*,
-                               const void*, void*, void*, int, int, float,
-                               hipStream_t);
-void dmx_launch_attention_bf16(const void*, const void*, const void*, void*,
-                               int, int, int, float, hipStream_t);
-void dmx_launch_attention_mfma_bf16(const void*, void*, int, int, int, int,
-                                    float, hipStream_t);
-void dmx_launch_bert_fused_bf16(const void*, const void*, const void*,
-                                const void*, const void*, void*, int, int,
-                                int, float, hipStream_t);
-void dmx_launch_bert_fused_probe(const void*, const void*, const void*,
-                                 const void*, const void*, void*, int, int,
-                                 int, float, int, hipStream_t);
-void dmx_launch_bert_fused_timed(const void*, const void*, const void*,
-                                 const void*, const void*, void*, void*, int,
-                                 int, int, float, hipStream_t);
-void dmx_launch_template_match(const void*, const void*, int, int,
-                               const void*, const void*, int, const void*,
-                               int, const void*, const void*, int, int,
-                               void*, void*, void*, void*, void*, void*,
-                               void*, int, int, hipStream_t);
-void dmx_launch_watch_hashes(const void*, int, const void*, const void*,
-                             const void*, int, const void*, const void*,
-                             int, const void*, int, int, int, void*,
-                             hipStream_t);
-void dmx_launch_hashset_insert(const void*, void*, int, int, int,
-                               hipStream_t);
-void dmx_launch_hashset_probe(const void*, const void*, int, int, int,
-                              void*, hipStream_t);
-void dmx_launch_edit_distance(const void*, const void*, int, const void*,
-                              const void*, int, int, void*, hipStream_t);
-}
+#include "kernels.h"
 
 namespace {
 
-hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
+// ---- launch contract helpers ------------------------------------------------
+// Every binding (1) validates each tensor it passes down with check_arg /
+// check_numel / check_same_shape, (2) checks devices LAST with DeviceScope,
+// so every other clause can be exercised with CPU tensors, (3) returns an
+// empty result instead of launching a zero-sized grid, (4) launches on the
+// current stream of the tensors' device and (5) reads the launch result.
 
-void check_bf16_2d(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.dtype() == torch::kBFloat16, name, " must be bf16");
+void check_arg(const torch::Tensor& t, const char* name, c10::ScalarType dtype,
+               int64_t dim) {
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.dim() == dim, name, " must be ", dim, "-D, got ", t.dim(),
+              "-D");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+
+void check_numel(const torch::Tensor& t, const char* name, int64_t n,
+                 const char* what) {
+  TORCH_CHECK(t.numel() == n, name, " must hold ", what, " = ", n,
+              " elements, got ", t.numel());
+}
+
+void check_same_shape(const torch::Tensor& t, const char* name,
+                      const torch::Tensor& ref, const char* ref_name) {
+  TORCH_CHECK(t.sizes() == ref.sizes(), name, " must be shaped like ",
+              ref_name, " ", ref.sizes(), ", got ", t.sizes());
+}
+
+// [B, n, 2] int32 capture table
+void check_caps(const torch::Tensor& t, const char* name, int64_t B) {
+  check_arg(t, name, torch::kInt32, 3);
+  TORCH_CHECK(t.size(0) == B && t.size(1) >= 1 && t.size(2) == 2, name,
+              " must be [B=", B, ", n>=1, 2], got ", t.sizes());
+}
+
+struct Arg {
+  const char* name;
+  const torch::Tensor& t;
+};
+
+// Device clause + launch scope: the first argument must live on a GPU and
+// every other one on the same GPU; that device is made current for the
+// scope's lifetime, so the current stream and the kernel launch belong to
+// the tensors' device rather than to whatever device the caller left set.
+class DeviceScope {
+ public:
+  DeviceScope(std::initializer_list<Arg> args) {
+    const Arg& first = *args.begin();
+    TORCH_CHECK(first.t.is_cuda(), first.name, " must be on a GPU, got ",
+                first.t.device());
+    for (const Arg& a : args)
+      TORCH_CHECK(a.t.device() == first.t.device(), a.name, " must be on ",
+                  first.name, "'s device ", first.t.device(), ", got ",
+                  a.t.device());
+    guard_.set_device(first.t.device());
+    stream_ = at::hip::getCurrentHIPStream().stream();
+  }
+  hipStream_t stream() const { return stream_; }
+
+ private:
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard_;
+  hipStream_t stream_ = nullptr;
+};
+
+const int16_t* bf16_in(const torch::Tensor& t) {
+  return static_cast<const int16_t*>(t.data_ptr());
+}
+int16_t* bf16_out(torch::Tensor& t) {
+  return static_cast<int16_t*>(t.data_ptr());
+}
+
+// ---- dense ops ----------------------------------------------------------------
 
 torch::Tensor fused_linear_bf16(torch::Tensor x, torch::Tensor wt,
                                 c10::optional<torch::Tensor> bias,
                                 int64_t epilogue) {
-  check_bf16_2d(x, "x");
-  check_bf16_2d(wt, "wt");
+  check_arg(x, "x", torch::kBFloat16, 2);
+  check_arg(wt, "wt", torch::kBFloat16, 2);
   const auto M = x.size(0), K = x.size(1), N = wt.size(0);
-  TORCH_CHECK(wt.size(1) == K, "wt must be [N, K] (pre-transposed weight)");
-  TORCH_CHECK(K % 64 == 0, "K must be a multiple of 64");
-  const void* bias_ptr = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->dtype() == torch::kFloat32 && bias->is_contiguous(),
-                "bias must be contiguous f32");
-    TORCH_CHECK(bias->numel() == N, "bias must be [N]");
-    bias_ptr = bias->data_ptr();
+  TORCH_CHECK(wt.size(1) == K, "wt must be [N, K=", K,
+              "] (pre-transposed weight), got ", wt.sizes());
+  TORCH_CHECK(K % GEMM_K_MULTIPLE == 0, "x: K must be a multiple of ",
+              GEMM_K_MULTIPLE, ", got ", K);
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 2, "epilogue must be 0, 1 or 2");
+  const bool has_bias = bias.has_value() && bias->defined();
+  if (has_bias) {
+    check_arg(*bias, "bias", torch::kFloat32, 1);
+    check_numel(*bias, "bias", N, "N");
   }
+  DeviceScope dev({{"x", x}, {"wt", wt}, {"bias", has_bias ? *bias : x}});
   auto C = torch::empty({M, N}, x.options());
-  dmx_launch_fused_linear_bf16(x.data_ptr(), wt.data_ptr(), bias_ptr,
-                               C.data_ptr(), (int)M, (int)N, (int)K,
-                               (int)epilogue, cur_stream());
+  if (M == 0 || N == 0) return C;
+  dmx_launch_fused_linear_bf16(bf16_in(x), bf16_in(wt),
+                               has_bias ? bias->data_ptr<float>() : nullptr,
+                               bf16_out(C), (int)M, (int)N, (int)K,
+                               (int)epilogue, dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return C;
 }
 
 torch::Tensor probe_mfma32(torch::Tensor A, torch::Tensor B) {
+  check_arg(A, "A", torch::kBFloat16, 2);
+  check_arg(B, "B", torch::kBFloat16, 2);
   TORCH_CHECK(A.size(0) == 32 && A.size(1) == 16, "A must be 32x16");
   TORCH_CHECK(B.size(0) == 16 && B.size(1) == 32, "B must be 16x32");
+  DeviceScope dev({{"A", A}, {"B", B}});
   auto D = torch::zeros({32, 32}, A.options().dtype(torch::kFloat32));
-  dmx_launch_probe_mfma32(A.data_ptr(), B.data_ptr(), D.data_ptr(),
-                          cur_stream());
+  dmx_launch_probe_mfma32(bf16_in(A), bf16_in(B), D.data_ptr<float>(),
+                          dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return D;
 }
 
 torch::Tensor probe_mfma(torch::Tensor A, torch::Tensor B, int64_t a_layout,
                          int64_t b_layout) {
-  check_bf16_2d(A, "A");
-  check_bf16_2d(B, "B");
+  check_arg(A, "A", torch::kBFloat16, 2);
+  check_arg(B, "B", torch::kBFloat16, 2);
   TORCH_CHECK(A.size(0) == 16 && A.size(1) == 32, "A must be 16x32");
   TORCH_CHECK(B.size(0) == 32 && B.size(1) == 16, "B must be 32x16");
-  auto D = torch::zeros({16, 16},
-                        A.options().dtype(torch::kFloat32));
-  dmx_launch_probe_mfma(A.data_ptr(), B.data_ptr(), D.data_ptr(),
-                        (int)a_layout, (int)b_layout, cur_stream());
+  DeviceScope dev({{"A", A}, {"B", B}});
+  auto D = torch::zeros({16, 16}, A.options().dtype(torch::kFloat32));
+  dmx_launch_probe_mfma(bf16_in(A), bf16_in(B), D.data_ptr<float>(),
+                        (int)a_layout, (int)b_layout, dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return D;
 }
 
@@ -109,123 +150,139 @@ std::vector<torch::Tensor> layernorm_bf16(torch::Tensor x,
                                           torch::Tensor gamma,
                                           torch::Tensor beta, double eps,
                                           bool want_xres) {
-  check_bf16_2d(x, "x");
+  check_arg(x, "x", torch::kBFloat16, 2);
   const auto M = x.size(0), D = x.size(1);
-  TORCH_CHECK(D % 64 == 0 && D <= 2048, "D must be a multiple of 64, <=2048");
-  const void* res_ptr = nullptr;
-  if (res.has_value() && res->defined()) {
-    check_bf16_2d(*res, "res");
-    res_ptr = res->data_ptr();
+  TORCH_CHECK(D % 64 == 0 && D <= LN_MAX_D,
+              "x: D must be a multiple of 64, <= ", LN_MAX_D, ", got ", D);
+  const bool has_res = res.has_value() && res->defined();
+  if (has_res) {
+    check_arg(*res, "res", torch::kBFloat16, 2);
+    check_same_shape(*res, "res", x, "x");
   }
+  check_arg(gamma, "gamma", torch::kBFloat16, 1);
+  check_numel(gamma, "gamma", D, "D");
+  check_arg(beta, "beta", torch::kBFloat16, 1);
+  check_numel(beta, "beta", D, "D");
+  DeviceScope dev({{"x", x},
+                   {"res", has_res ? *res : x},
+                   {"gamma", gamma},
+                   {"beta", beta}});
   auto y = torch::empty_like(x);
   torch::Tensor xres;
-  void* xres_ptr = nullptr;
-  if (want_xres) {
-    xres = torch::empty_like(x);
-    xres_ptr = xres.data_ptr();
+  if (want_xres) xres = torch::empty_like(x);
+  if (M > 0) {
+    dmx_launch_layernorm_bf16(bf16_in(x), has_res ? bf16_in(*res) : nullptr,
+                              bf16_in(gamma), bf16_in(beta), bf16_out(y),
+                              want_xres ? bf16_out(xres) : nullptr, (int)M,
+                              (int)D, (float)eps, dev.stream());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
-  dmx_launch_layernorm_bf16(x.data_ptr(), res_ptr, gamma.data_ptr(),
-                            beta.data_ptr(), y.data_ptr(), xres_ptr, (int)M,
-                            (int)D, (float)eps, cur_stream());
   if (want_xres) return {y, xres};
   return {y};
 }
 
 torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k,
                              torch::Tensor v, double scale) {
-  TORCH_CHECK(q.dim() == 3, "q must be [BH, S, Dh]");
-  check_bf16_2d(q.flatten(0, 1), "q");
+  check_arg(q, "q", torch::kBFloat16, 3);  // [BH, S, Dh]
+  check_arg(k, "k", torch::kBFloat16, 3);
+  check_same_shape(k, "k", q, "q");
+  check_arg(v, "v", torch::kBFloat16, 3);
+  check_same_shape(v, "v", q, "q");
   const auto BH = q.size(0), S = q.size(1), Dh = q.size(2);
-  TORCH_CHECK(S <= 128 && Dh <= 64 && Dh % 8 == 0,
-              "attention kernel supports S<=128, Dh<=64 (multiple of 8)");
-  TORCH_CHECK((S * Dh) % 8 == 0, "S*Dh must be a multiple of 8");
+  TORCH_CHECK(S >= 1 && S <= ATTN_MAX_S && Dh >= 8 && Dh <= ATTN_MAX_DH &&
+                  Dh % 8 == 0,
+              "q: attention kernel supports 1<=S<=", ATTN_MAX_S, ", Dh<=",
+              ATTN_MAX_DH, " (multiple of 8), got ", q.sizes());
+  DeviceScope dev({{"q", q}, {"k", k}, {"v", v}});
   auto o = torch::empty_like(q);
-  dmx_launch_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                            o.data_ptr(), (int)BH, (int)S, (int)Dh,
-                            (float)scale, cur_stream());
+  if (BH == 0) return o;
+  dmx_launch_attention_bf16(bf16_in(q), bf16_in(k), bf16_in(v), bf16_out(o),
+                            (int)BH, (int)S, (int)Dh, (float)scale,
+                            dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return o;
 }
 
 torch::Tensor attention_qkv_bf16(torch::Tensor qkv, int64_t S, int64_t H,
                                  int64_t Dh, double scale) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kBFloat16 &&
-                  qkv.is_contiguous(),
-              "qkv must be contiguous bf16 on GPU");
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * H * Dh,
-              "qkv must be [B, S, 3*H*Dh]");
-  TORCH_CHECK(S % 32 == 0 && S <= 128, "MFMA attention needs S%32==0, S<=128");
-  TORCH_CHECK(Dh == 32 || Dh == 64, "MFMA attention needs Dh in {32,64}");
+  check_arg(qkv, "qkv", torch::kBFloat16, 3);
+  TORCH_CHECK(S >= 32 && S % 32 == 0 && S <= ATTN_MAX_S,
+              "S: MFMA attention needs S%32==0, 32<=S<=", ATTN_MAX_S, ", got ",
+              S);
+  TORCH_CHECK(Dh == 32 || Dh == 64, "Dh: MFMA attention needs Dh in {32,64}");
+  TORCH_CHECK(H >= 1, "H must be >= 1");
+  TORCH_CHECK(qkv.size(1) == S && qkv.size(2) == 3 * H * Dh,
+              "qkv must be [B, S=", S, ", 3*H*Dh=", 3 * H * Dh, "], got ",
+              qkv.sizes());
+  DeviceScope dev({{"qkv", qkv}});
   const auto B = qkv.size(0);
   auto O = torch::empty({B, S, H * Dh}, qkv.options());
-  dmx_launch_attention_mfma_bf16(qkv.data_ptr(), O.data_ptr(), (int)B, (int)S,
-                                 (int)H, (int)Dh, (float)scale, cur_stream());
+  if (B == 0) return O;
+  dmx_launch_attention_mfma_bf16(bf16_in(qkv), bf16_out(O), (int)B, (int)S,
+                                 (int)H, (int)Dh, (float)scale, dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return O;
+}
+
+// ---- fused BERT-tiny ------------------------------------------------------------
+
+// Everything the three fused entry points share, device clause last.
+DeviceScope check_bert_fused_args(const torch::Tensor& lines,
+                                  const torch::Tensor& start,
+                                  const torch::Tensor& end,
+                                  const torch::Tensor& wb,
+                                  const torch::Tensor& fb, int64_t n_layers) {
+  check_arg(lines, "lines", torch::kUInt8, 2);
+  const auto B = lines.size(0);
+  check_arg(start, "start", torch::kInt32, 1);
+  check_numel(start, "start", B, "B");
+  check_arg(end, "end", torch::kInt32, 1);
+  check_numel(end, "end", B, "B");
+  TORCH_CHECK(n_layers >= 1, "n_layers must be >= 1, got ", n_layers);
+  check_arg(wb, "wb", torch::kBFloat16, 1);
+  check_numel(wb, "wb", bert_fused_wb_elems((int)n_layers),
+              "bert_fused_wb_elems(n_layers)");
+  check_arg(fb, "fb", torch::kFloat32, 1);
+  check_numel(fb, "fb", bert_fused_fb_elems((int)n_layers),
+              "bert_fused_fb_elems(n_layers)");
+  return DeviceScope(
+      {{"lines", lines}, {"start", start}, {"end", end}, {"wb", wb}, {"fb", fb}});
 }
 
 torch::Tensor bert_fused_bf16(torch::Tensor lines, torch::Tensor start,
                               torch::Tensor end, torch::Tensor wb,
                               torch::Tensor fb, int64_t n_layers,
                               double eps) {
-  TORCH_CHECK(lines.is_cuda() && lines.dtype() == torch::kUInt8 &&
-                  lines.is_contiguous(),
-              "lines must be contiguous u8 on GPU");
-  TORCH_CHECK(wb.dtype() == torch::kBFloat16 && wb.is_contiguous());
-  TORCH_CHECK(fb.dtype() == torch::kFloat32 && fb.is_contiguous());
-  TORCH_CHECK(start.dtype() == torch::kInt32 && end.dtype() == torch::kInt32);
+  DeviceScope dev = check_bert_fused_args(lines, start, end, wb, fb, n_layers);
   const auto B = lines.size(0), max_len = lines.size(1);
-  auto scores = torch::empty(
-      {B}, torch::TensorOptions().dtype(torch::kFloat32).device(lines.device()));
-  dmx_launch_bert_fused_bf16(lines.data_ptr(), start.data_ptr(),
-                             end.data_ptr(), wb.data_ptr(), fb.data_ptr(),
-                             scores.data_ptr(), (int)B, (int)max_len,
-                             (int)n_layers, (float)eps, cur_stream());
+  auto scores = torch::empty({B}, lines.options().dtype(torch::kFloat32));
+  if (B == 0) return scores;
+  C10_HIP_CHECK(dmx_launch_bert_fused_bf16(
+      lines.data_ptr<uint8_t>(), start.data_ptr<int32_t>(),
+      end.data_ptr<int32_t>(), bf16_in(wb), fb.data_ptr<float>(),
+      scores.data_ptr<float>(), (int)B, (int)max_len, (int)n_layers,
+      (float)eps, dev.stream()));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return scores;
-}
-
-std::vector<torch::Tensor> template_match(
-    torch::Tensor lines, torch::Tensor line_len, torch::Tensor fmt_bytes,
-    torch::Tensor fmt_seg_off, torch::Tensor seg_bytes, torch::Tensor seg_off,
-    torch::Tensor tpl_seg_start, bool lower, int64_t max_fmt_caps,
-    int64_t max_caps) {
-  TORCH_CHECK(lines.is_cuda() && lines.dtype() == torch::kUInt8 &&
-                  lines.is_contiguous() && lines.dim() == 2,
-              "lines must be contiguous u8 [B, max_len] on GPU");
-  const auto B = lines.size(0), max_len = lines.size(1);
-  TORCH_CHECK(max_len <= 512, "max_len must be <= 512 (TM_MAX_LINE)");
-  const int nf_seg = fmt_seg_off.numel() > 0 ? (int)fmt_seg_off.numel() - 1 : 0;
-  const int n_tpl = (int)tpl_seg_start.numel() - 1;
-  auto opts = torch::TensorOptions().dtype(torch::kInt32).device(lines.device());
-  auto event_id = torch::empty({B}, opts);
-  auto fmt_caps = torch::zeros({B, max_fmt_caps, 2}, opts);
-  auto n_fmt_caps = torch::zeros({B}, opts);
-  auto caps = torch::zeros({B, max_caps, 2}, opts);
-  auto n_caps = torch::zeros({B}, opts);
-  auto span_start = torch::empty({B}, opts);
-  auto span_end = torch::empty({B}, opts);
-  dmx_launch_template_match(
-      lines.data_ptr(), line_len.data_ptr(), (int)B, (int)max_len,
-      fmt_bytes.numel() ? fmt_bytes.data_ptr() : nullptr,
-      fmt_seg_off.numel() ? fmt_seg_off.data_ptr() : nullptr, nf_seg,
-      seg_bytes.data_ptr(), (int)seg_bytes.numel(), seg_off.data_ptr(),
-      tpl_seg_start.data_ptr(), n_tpl, lower ? 1 : 0, event_id.data_ptr(),
-      fmt_caps.data_ptr(), n_fmt_caps.data_ptr(), caps.data_ptr(),
-      n_caps.data_ptr(), span_start.data_ptr(), span_end.data_ptr(),
-      (int)max_fmt_caps, (int)max_caps, cur_stream());
-  return {event_id, fmt_caps, n_fmt_caps, caps, n_caps, span_start, span_end};
 }
 
 torch::Tensor bert_fused_probe(torch::Tensor lines, torch::Tensor start,
                                torch::Tensor end, torch::Tensor wb,
                                torch::Tensor fb, int64_t n_layers, double eps,
                                int64_t phase_mask) {
+  TORCH_CHECK(phase_mask >= 0 && phase_mask <= INT32_MAX &&
+                  dmx_bert_fused_probe_mask_known((int)phase_mask),
+              "phase_mask ", phase_mask, " names no compiled probe variant");
+  DeviceScope dev = check_bert_fused_args(lines, start, end, wb, fb, n_layers);
   const auto B = lines.size(0), max_len = lines.size(1);
-  auto scores = torch::empty(
-      {B}, torch::TensorOptions().dtype(torch::kFloat32).device(lines.device()));
-  dmx_launch_bert_fused_probe(lines.data_ptr(), start.data_ptr(),
-                              end.data_ptr(), wb.data_ptr(), fb.data_ptr(),
-                              scores.data_ptr(), (int)B, (int)max_len,
-                              (int)n_layers, (float)eps, (int)phase_mask,
-                              cur_stream());
+  auto scores = torch::empty({B}, lines.options().dtype(torch::kFloat32));
+  if (B == 0) return scores;
+  C10_HIP_CHECK(dmx_launch_bert_fused_probe(
+      lines.data_ptr<uint8_t>(), start.data_ptr<int32_t>(),
+      end.data_ptr<int32_t>(), bf16_in(wb), fb.data_ptr<float>(),
+      scores.data_ptr<float>(), (int)B, (int)max_len, (int)n_layers,
+      (float)eps, (int)phase_mask, dev.stream()));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return scores;
 }
 
@@ -235,32 +292,149 @@ std::vector<torch::Tensor> bert_fused_timed(torch::Tensor lines,
                                             torch::Tensor wb,
                                             torch::Tensor fb,
                                             int64_t n_layers, double eps) {
+  DeviceScope dev = check_bert_fused_args(lines, start, end, wb, fb, n_layers);
   const auto B = lines.size(0), max_len = lines.size(1);
-  auto scores = torch::empty(
-      {B}, torch::TensorOptions().dtype(torch::kFloat32).device(lines.device()));
-  auto stamps = torch::zeros(
-      {B, 8, 22},
-      torch::TensorOptions().dtype(torch::kInt64).device(lines.device()));
-  dmx_launch_bert_fused_timed(lines.data_ptr(), start.data_ptr(),
-                              end.data_ptr(), wb.data_ptr(), fb.data_ptr(),
-                              scores.data_ptr(), stamps.data_ptr(), (int)B,
-                              (int)max_len, (int)n_layers, (float)eps,
-                              cur_stream());
+  auto scores = torch::empty({B}, lines.options().dtype(torch::kFloat32));
+  auto stamps = torch::zeros({B, BF_WAVES, BF_NSTAMP},
+                             lines.options().dtype(torch::kInt64));
+  if (B == 0) return {scores, stamps};
+  C10_HIP_CHECK(dmx_launch_bert_fused_timed(
+      lines.data_ptr<uint8_t>(), start.data_ptr<int32_t>(),
+      end.data_ptr<int32_t>(), bf16_in(wb), fb.data_ptr<float>(),
+      scores.data_ptr<float>(), stamps.data_ptr<int64_t>(), (int)B,
+      (int)max_len, (int)n_layers, (float)eps, dev.stream()));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {scores, stamps};
+}
+
+// The fused kernel's geometry and blob layout, for the Python side to pack
+// against and to compare a model config with (no copy of these numbers
+// lives in Python). Keys named like BertTinyConfig fields where one exists.
+py::dict bert_fused_layout(int64_t n_layers) {
+  TORCH_CHECK(n_layers >= 0 && n_layers <= 1024,
+              "n_layers must be in [0, 1024], got ", n_layers);
+  const int64_t wb_score = WB_LAYER0 + n_layers * LW_SIZE;
+  py::dict d;
+  d["max_seq"] = BF_S;
+  d["hidden"] = BF_H;
+  d["heads"] = BF_HEADS;
+  d["head_dim"] = BF_DH;
+  d["ffn"] = BF_FFN;
+  d["vocab_size"] = BF_VOCAB;
+  d["waves"] = BF_WAVES;
+  d["nstamp"] = BF_NSTAMP;
+  d["lds_bytes"] = BF_LDS_BYTES;
+  d["wb_elems"] = bert_fused_wb_elems((int)n_layers);
+  d["fb_elems"] = bert_fused_fb_elems((int)n_layers);
+  d["wb_tok"] = WB_TOK;
+  d["wb_pos"] = WB_POS;
+  d["wb_layer0"] = WB_LAYER0;
+  d["wb_score"] = wb_score;
+  d["lw_qkv"] = LW_QKV;
+  d["lw_wo"] = LW_WO;
+  d["lw_w1"] = LW_W1;
+  d["lw_w2"] = LW_W2;
+  d["lw_ln1g"] = LW_LN1G;
+  d["lw_ln1b"] = LW_LN1B;
+  d["lw_ln2g"] = LW_LN2G;
+  d["lw_ln2b"] = LW_LN2B;
+  d["lw_size"] = LW_SIZE;
+  d["fb_bqkv"] = FB_BQKV;
+  d["fb_bo"] = FB_BO;
+  d["fb_b1"] = FB_B1;
+  d["fb_b2"] = FB_B2;
+  d["fb_size"] = FB_SIZE;
+  d["fb_score"] = n_layers * FB_SIZE;
+  return d;
+}
+
+// ---- parser / detector ------------------------------------------------------------
+
+std::vector<torch::Tensor> template_match(
+    torch::Tensor lines, torch::Tensor line_len, torch::Tensor fmt_bytes,
+    torch::Tensor fmt_seg_off, torch::Tensor seg_bytes, torch::Tensor seg_off,
+    torch::Tensor tpl_seg_start, bool lower, int64_t max_fmt_caps,
+    int64_t max_caps) {
+  check_arg(lines, "lines", torch::kUInt8, 2);
+  const auto B = lines.size(0), max_len = lines.size(1);
+  TORCH_CHECK(max_len <= TM_MAX_LINE, "lines: max_len must be <= ",
+              TM_MAX_LINE, " (TM_MAX_LINE), got ", max_len);
+  check_arg(line_len, "line_len", torch::kInt32, 1);
+  check_numel(line_len, "line_len", B, "B");
+  check_arg(fmt_bytes, "fmt_bytes", torch::kUInt8, 1);
+  check_arg(fmt_seg_off, "fmt_seg_off", torch::kInt32, 1);
+  check_arg(seg_bytes, "seg_bytes", torch::kUInt8, 1);
+  check_arg(seg_off, "seg_off", torch::kInt32, 1);
+  check_arg(tpl_seg_start, "tpl_seg_start", torch::kInt32, 1);
+  TORCH_CHECK(seg_off.numel() >= 1, "seg_off must hold at least one offset");
+  TORCH_CHECK(tpl_seg_start.numel() >= 1,
+              "tpl_seg_start must hold at least one offset");
+  TORCH_CHECK(max_fmt_caps >= 1 && max_caps >= 1,
+              "max_fmt_caps and max_caps must be >= 1");
+  // the kernel stages the whole segment blob in LDS and its launcher does
+  // not raise the per-kernel dynamic-LDS limit
+  TORCH_CHECK(seg_bytes.numel() <= LDS_DEFAULT_LIMIT &&
+                  tm_lds_bytes((int)seg_bytes.numel()) <= LDS_DEFAULT_LIMIT,
+              "seg_bytes: a template segment blob of ", seg_bytes.numel(),
+              " bytes needs more than the ", LDS_DEFAULT_LIMIT,
+              " bytes of LDS the kernel may use (",
+              TM_WAVES * TM_MAX_LINE, " of them hold the staged lines)");
+  DeviceScope dev({{"lines", lines},
+                   {"line_len", line_len},
+                   {"fmt_bytes", fmt_bytes},
+                   {"fmt_seg_off", fmt_seg_off},
+                   {"seg_bytes", seg_bytes},
+                   {"seg_off", seg_off},
+                   {"tpl_seg_start", tpl_seg_start}});
+  const int nf_seg = fmt_seg_off.numel() > 0 ? (int)fmt_seg_off.numel() - 1 : 0;
+  const int n_tpl = (int)tpl_seg_start.numel() - 1;
+  auto opts = lines.options().dtype(torch::kInt32);
+  auto event_id = torch::empty({B}, opts);
+  auto fmt_caps = torch::zeros({B, max_fmt_caps, 2}, opts);
+  auto n_fmt_caps = torch::zeros({B}, opts);
+  auto caps = torch::zeros({B, max_caps, 2}, opts);
+  auto n_caps = torch::zeros({B}, opts);
+  auto span_start = torch::empty({B}, opts);
+  auto span_end = torch::empty({B}, opts);
+  if (B > 0) {
+    dmx_launch_template_match(
+        lines.data_ptr<uint8_t>(), line_len.data_ptr<int32_t>(), (int)B,
+        (int)max_len,
+        fmt_bytes.numel() ? fmt_bytes.data_ptr<uint8_t>() : nullptr,
+        fmt_seg_off.numel() ? fmt_seg_off.data_ptr<int32_t>() : nullptr,
+        nf_seg, seg_bytes.data_ptr<uint8_t>(), (int)seg_bytes.numel(),
+        seg_off.data_ptr<int32_t>(), tpl_seg_start.data_ptr<int32_t>(), n_tpl,
+        lower ? 1 : 0, event_id.data_ptr<int32_t>(),
+        fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
+        caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(),
+        span_start.data_ptr<int32_t>(), span_end.data_ptr<int32_t>(),
+        (int)max_fmt_caps, (int)max_caps, dev.stream());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return {event_id, fmt_caps, n_fmt_caps, caps, n_caps, span_start, span_end};
 }
 
 torch::Tensor edit_distance(torch::Tensor A, torch::Tensor a_len,
                             torch::Tensor B, torch::Tensor b_len) {
-  TORCH_CHECK(A.is_cuda() && A.dtype() == torch::kUInt8 && A.is_contiguous());
-  TORCH_CHECK(B.is_cuda() && B.dtype() == torch::kUInt8 && B.is_contiguous());
-  TORCH_CHECK(A.size(1) == B.size(1), "A and B must share max_len");
-  TORCH_CHECK(A.size(1) <= 256, "edit_distance supports max_len<=256");
+  check_arg(A, "A", torch::kUInt8, 2);
+  check_arg(B, "B", torch::kUInt8, 2);
   const auto Na = A.size(0), Nb = B.size(0), max_len = A.size(1);
-  auto dist = torch::empty(
-      {Na, Nb}, torch::TensorOptions().dtype(torch::kInt32).device(A.device()));
-  dmx_launch_edit_distance(A.data_ptr(), a_len.data_ptr(), (int)Na,
-                           B.data_ptr(), b_len.data_ptr(), (int)Nb,
-                           (int)max_len, dist.data_ptr(), cur_stream());
+  TORCH_CHECK(B.size(1) == max_len, "B must share A's max_len ", max_len,
+              ", got ", B.size(1));
+  TORCH_CHECK(max_len <= ED_MAX_LEN, "A: edit_distance supports max_len<=",
+              ED_MAX_LEN, ", got ", max_len);
+  check_arg(a_len, "a_len", torch::kInt32, 1);
+  check_numel(a_len, "a_len", Na, "Na");
+  check_arg(b_len, "b_len", torch::kInt32, 1);
+  check_numel(b_len, "b_len", Nb, "Nb");
+  DeviceScope dev({{"A", A}, {"a_len", a_len}, {"B", B}, {"b_len", b_len}});
+  auto dist = torch::empty({Na, Nb}, A.options().dtype(torch::kInt32));
+  if (Na == 0 || Nb == 0) return dist;
+  dmx_launch_edit_distance(A.data_ptr<uint8_t>(), a_len.data_ptr<int32_t>(),
+                           (int)Na, B.data_ptr<uint8_t>(),
+                           b_len.data_ptr<int32_t>(), (int)Nb, (int)max_len,
+                           dist.data_ptr<int32_t>(), dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dist;
 }
 
@@ -268,36 +442,74 @@ torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
                            torch::Tensor caps, torch::Tensor n_caps,
                            torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
                            torch::Tensor specs, bool lower) {
+  check_arg(lines, "lines", torch::kUInt8, 2);
   const auto B = lines.size(0), max_len = lines.size(1);
+  check_arg(event_id, "event_id", torch::kInt32, 1);
+  check_numel(event_id, "event_id", B, "B");
+  check_caps(caps, "caps", B);
+  check_arg(n_caps, "n_caps", torch::kInt32, 1);
+  check_numel(n_caps, "n_caps", B, "B");
+  check_caps(fmt_caps, "fmt_caps", B);
+  check_arg(n_fmt_caps, "n_fmt_caps", torch::kInt32, 1);
+  check_numel(n_fmt_caps, "n_fmt_caps", B, "B");
+  check_arg(specs, "specs", torch::kInt32, 2);
+  TORCH_CHECK(specs.size(1) == 4,
+              "specs must be int32 [W, 4] (kind, event, pos, pad), got ",
+              specs.sizes());
   const auto W = specs.size(0);
-  TORCH_CHECK(specs.dtype() == torch::kInt32 && specs.size(1) == 4,
-              "specs must be int32 [W, 4] (kind, event, pos, pad)");
-  auto hashes = torch::zeros(
-      {B, W}, torch::TensorOptions().dtype(torch::kInt64).device(lines.device()));
+  DeviceScope dev({{"lines", lines},
+                   {"event_id", event_id},
+                   {"caps", caps},
+                   {"n_caps", n_caps},
+                   {"fmt_caps", fmt_caps},
+                   {"n_fmt_caps", n_fmt_caps},
+                   {"specs", specs}});
+  auto hashes = torch::zeros({B, W}, lines.options().dtype(torch::kInt64));
+  if (B == 0 || W == 0) return hashes;
   dmx_launch_watch_hashes(
-      lines.data_ptr(), (int)max_len, event_id.data_ptr(), caps.data_ptr(),
-      n_caps.data_ptr(), (int)caps.size(1), fmt_caps.data_ptr(),
-      n_fmt_caps.data_ptr(), (int)fmt_caps.size(1), specs.data_ptr(), (int)W,
-      (int)B, lower ? 1 : 0, hashes.data_ptr(), cur_stream());
+      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
+      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
+      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
+      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)W, (int)B,
+      lower ? 1 : 0, hashes.data_ptr<int64_t>(), dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return hashes;
 }
 
+// hashes [B, W] int64 against tables [W, capacity] int64
+void check_hashset_args(const torch::Tensor& hashes,
+                        const torch::Tensor& tables) {
+  check_arg(hashes, "hashes", torch::kInt64, 2);
+  check_arg(tables, "tables", torch::kInt64, 2);
+  const auto W = hashes.size(1), cap = tables.size(1);
+  TORCH_CHECK(tables.size(0) == W, "tables must be [W=", W,
+              ", capacity] to match hashes [B, W], got ", tables.sizes());
+  TORCH_CHECK(cap >= 1 && (cap & (cap - 1)) == 0,
+              "tables: capacity must be a power of two, got ", cap);
+}
+
 void hashset_insert(torch::Tensor hashes, torch::Tensor tables) {
+  check_hashset_args(hashes, tables);
+  DeviceScope dev({{"hashes", hashes}, {"tables", tables}});
   const auto B = hashes.size(0), W = hashes.size(1);
-  TORCH_CHECK(tables.size(0) == W, "tables must be [W, capacity]");
-  const auto cap = tables.size(1);
-  TORCH_CHECK((cap & (cap - 1)) == 0, "capacity must be a power of two");
-  dmx_launch_hashset_insert(hashes.data_ptr(), tables.data_ptr(), (int)B,
-                            (int)W, (int)cap, cur_stream());
+  if (B == 0 || W == 0) return;
+  dmx_launch_hashset_insert(hashes.data_ptr<int64_t>(),
+                            tables.data_ptr<int64_t>(), (int)B, (int)W,
+                            (int)tables.size(1), dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 torch::Tensor hashset_probe(torch::Tensor hashes, torch::Tensor tables) {
+  check_hashset_args(hashes, tables);
+  DeviceScope dev({{"hashes", hashes}, {"tables", tables}});
   const auto B = hashes.size(0), W = hashes.size(1);
-  const auto cap = tables.size(1);
-  auto unseen = torch::zeros(
-      {B, W}, torch::TensorOptions().dtype(torch::kInt32).device(hashes.device()));
-  dmx_launch_hashset_probe(hashes.data_ptr(), tables.data_ptr(), (int)B,
-                           (int)W, (int)cap, unseen.data_ptr(), cur_stream());
+  auto unseen = torch::zeros({B, W}, hashes.options().dtype(torch::kInt32));
+  if (B == 0 || W == 0) return unseen;
+  dmx_launch_hashset_probe(hashes.data_ptr<int64_t>(),
+                           tables.data_ptr<int64_t>(), (int)B, (int)W,
+                           (int)tables.size(1), unseen.data_ptr<int32_t>(),
+                           dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return unseen;
 }
 
@@ -325,6 +537,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "phase-masked probe variant of the fused BERT kernel");
   m.def("bert_fused_timed", &bert_fused_timed,
         "fused kernel with per-wave phase timestamps (diagnostic)");
+  m.def("bert_fused_layout", &bert_fused_layout,
+        "geometry, blob sizes and named offsets of the fused BERT kernel");
   m.def("template_match", &template_match, "batched wildcard template match");
   m.def("watch_hashes", &watch_hashes, "hash watched capture spans");
   m.def("hashset_insert", &hashset_insert, "insert hashes into GPU sets");

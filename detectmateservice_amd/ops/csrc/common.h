@@ -11,16 +11,6 @@
 
 #define DMX_WAVE 64
 
-#define DMX_HIP_CHECK(expr)                                                    \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__,       \
-             __LINE__);                                                        \
-      abort();                                                                 \
-    }                                                                          \
-  } while (0)
-
 // Vector types for wide loads (Guideline 13: always vectorize bf16 as
 // short4/short8 reinterpret — 8-16 B/lane).
 typedef __attribute__((ext_vector_type(4))) short short4v;

@@ -9,9 +9,9 @@
 // across lanes). Diagonal arrays live in LDS; a wave-local
 // s_waitcnt lgkmcnt(0) orders neighbor-lane reads between diagonals.
 #include "common.h"
+#include "kernels.h"
 
-#define ED_WAVES 4
-#define ED_MAX_LEN 256
+#define ED_WAVES 4  // ED_MAX_LEN: kernels.h
 
 extern "C" __global__ __launch_bounds__(ED_WAVES * DMX_WAVE)
 void dmx_edit_distance(
@@ -99,15 +99,13 @@ void dmx_edit_distance(
 }
 
 extern "C" void dmx_launch_edit_distance(
-    const void* A, const void* a_len, int Na, const void* B,
-    const void* b_len, int Nb, int max_len, void* dist,
+    const uint8_t* A, const int32_t* a_len, int Na, const uint8_t* B,
+    const int32_t* b_len, int Nb, int max_len, int32_t* dist,
     hipStream_t stream) {
   const long pairs = (long)Na * Nb;
   const int grid = (int)((pairs + ED_WAVES - 1) / ED_WAVES);
   const int wave_bytes = 2 * ED_MAX_LEN + 3 * (ED_MAX_LEN + 1) * 2 + 16;
   const size_t lds = (size_t)ED_WAVES * wave_bytes;
   hipLaunchKernelGGL(dmx_edit_distance, dim3(grid), dim3(ED_WAVES * DMX_WAVE),
-                     lds, stream, (const unsigned char*)A, (const int*)a_len,
-                     Na, (const unsigned char*)B, (const int*)b_len, Nb,
-                     max_len, (int*)dist);
+                     lds, stream, A, a_len, Na, B, b_len, Nb, max_len, dist);
 }

@@ -19,6 +19,7 @@
 // delegates to sklearn/numpy in `detectmatelibrary`.
 
 #include "common.h"
+#include "kernels.h"
 
 #define BM 128
 #define BN 128
@@ -167,15 +168,14 @@ void dmx_fused_linear_bf16(
 }
 
 extern "C" void dmx_launch_fused_linear_bf16(
-    const void* A, const void* Wt, const void* bias, void* C,
+    const int16_t* A, const int16_t* Wt, const float* bias, int16_t* C,
     int M, int N, int K, int epilogue, hipStream_t stream) {
   const int grid_m = (M + BM - 1) / BM;
   const int grid_n = (N + BN - 1) / BN;
   dim3 grid(grid_m * grid_n);
   dim3 block(THREADS);
   hipLaunchKernelGGL(dmx_fused_linear_bf16, grid, block, 0, stream,
-                     (const short*)A, (const short*)Wt, (const float*)bias,
-                     (short*)C, M, N, K, epilogue, grid_m);
+                     A, Wt, bias, C, M, N, K, epilogue, grid_m);
 }
 
 // ---------------------------------------------------------------------------
@@ -212,11 +212,10 @@ extern "C" __global__ void dmx_probe_mfma_16x16x32(
 }
 
 extern "C" void dmx_launch_probe_mfma(
-    const void* A, const void* B, void* D, int a_layout, int b_layout,
+    const int16_t* A, const int16_t* B, float* D, int a_layout, int b_layout,
     hipStream_t stream) {
   hipLaunchKernelGGL(dmx_probe_mfma_16x16x32, dim3(1), dim3(64), 0, stream,
-                     (const short*)A, (const short*)B, (float*)D, a_layout,
-                     b_layout);
+                     A, B, D, a_layout, b_layout);
 }
 
 // ---------------------------------------------------------------------------
@@ -251,8 +250,8 @@ extern "C" __global__ void dmx_probe_mfma_32x32x16(
   }
 }
 
-extern "C" void dmx_launch_probe_mfma32(const void* A, const void* B, void* D,
-                                        hipStream_t stream) {
+extern "C" void dmx_launch_probe_mfma32(const int16_t* A, const int16_t* B,
+                                        float* D, hipStream_t stream) {
   hipLaunchKernelGGL(dmx_probe_mfma_32x32x16, dim3(1), dim3(64), 0, stream,
-                     (const short*)A, (const short*)B, (float*)D);
+                     A, B, D);
 }

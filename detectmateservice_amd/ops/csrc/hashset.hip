@@ -10,6 +10,7 @@
 // Tables: [W, capacity] u64, 0 = empty (hashes are forced odd). Linear
 // probing; capacity is a power of two sized >= 4x expected cardinality.
 #include "common.h"
+#include "kernels.h"
 
 #define EMPTY_KEY 0ull
 
@@ -119,23 +120,22 @@ void dmx_hashset_probe(
 }
 
 extern "C" void dmx_launch_watch_hashes(
-    const void* lines, int max_len, const void* event_id, const void* caps,
-    const void* n_caps, int max_caps, const void* fmt_caps,
-    const void* n_fmt_caps, int max_fmt_caps, const void* specs, int W,
-    int B, int lower, void* hashes, hipStream_t stream) {
+    const uint8_t* lines, int max_len, const int32_t* event_id,
+    const int32_t* caps, const int32_t* n_caps, int max_caps,
+    const int32_t* fmt_caps, const int32_t* n_fmt_caps, int max_fmt_caps,
+    const int32_t* specs, int W, int B, int lower, int64_t* hashes,
+    hipStream_t stream) {
   const long total = (long)B * W;
   const int grid = (int)((total + 255) / 256);
   hipLaunchKernelGGL(dmx_watch_hashes, dim3(grid), dim3(256), 0, stream,
-                     (const unsigned char*)lines, max_len,
-                     (const int*)event_id, (const int*)caps,
-                     (const int*)n_caps, max_caps, (const int*)fmt_caps,
-                     (const int*)n_fmt_caps, max_fmt_caps,
+                     lines, max_len, event_id, caps, n_caps, max_caps,
+                     fmt_caps, n_fmt_caps, max_fmt_caps,
                      (const WatchSpec*)specs, W, B, lower,
                      (unsigned long long*)hashes);
 }
 
 extern "C" void dmx_launch_hashset_insert(
-    const void* hashes, void* tables, int B, int W, int capacity,
+    const int64_t* hashes, int64_t* tables, int B, int W, int capacity,
     hipStream_t stream) {
   const long total = (long)B * W;
   const int grid = (int)((total + 255) / 256);
@@ -145,12 +145,12 @@ extern "C" void dmx_launch_hashset_insert(
 }
 
 extern "C" void dmx_launch_hashset_probe(
-    const void* hashes, const void* tables, int B, int W, int capacity,
-    void* unseen, hipStream_t stream) {
+    const int64_t* hashes, const int64_t* tables, int B, int W, int capacity,
+    int32_t* unseen, hipStream_t stream) {
   const long total = (long)B * W;
   const int grid = (int)((total + 255) / 256);
   hipLaunchKernelGGL(dmx_hashset_probe, dim3(grid), dim3(256), 0, stream,
                      (const unsigned long long*)hashes,
                      (const unsigned long long*)tables, B, W, capacity,
-                     (int*)unseen);
+                     unseen);
 }

@@ -1,0 +1,167 @@
+// The launch boundary between the torch bindings and the HIP kernels.
+//
+// Every dmx_launch_* is declared HERE and nowhere else. bindings.cpp and
+// each .hip that defines a launcher include this header, so a parameter
+// added or reordered on one side only is a "conflicting types" compile
+// error instead of garbage handed to the GPU (extern "C" names carry no
+// signature). The header also owns every limit and layout constant that
+// both sides need; it is host-includable and needs only the HIP runtime
+// API header.
+//
+// Pointer conventions: bf16 tensors travel as int16_t (raw bits), u8 as
+// uint8_t, int32 as int32_t, int64 hash words as int64_t (the kernels
+// reinterpret them as unsigned 64-bit).
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+// ---- limits the bindings check before launch -------------------------------
+constexpr int GEMM_K_MULTIPLE = 64;   // fused_linear: K % 64 == 0 (BK tile)
+constexpr int LN_MAX_D = 2048;        // layernorm: D % 64 == 0, D <= 2048
+constexpr int ATTN_MAX_S = 128;       // attention (VALU and MFMA): S <= 128
+constexpr int ATTN_MAX_DH = 64;       // attention: Dh <= 64
+constexpr int AM_WAVES = 4;           // MFMA attention: waves per (b, h)
+constexpr int ED_MAX_LEN = 256;       // edit_distance: bytes per string
+constexpr int TM_WAVES = 4;           // template_match: lines per workgroup
+constexpr int TM_MAX_LINE = 512;      // template_match: bytes per line
+constexpr int LDS_DEFAULT_LIMIT = 64 * 1024;  // dynamic LDS without opt-in
+
+// Dynamic LDS of dmx_template_match: the segment blob (16-B rounded) plus
+// one staged line per wave. The kernel carves its arena the same way.
+constexpr int tm_seg_lds_bytes(int seg_bytes_len) {
+  return (seg_bytes_len + 15) & ~15;
+}
+constexpr size_t tm_lds_bytes(int seg_bytes_len) {
+  return tm_seg_lds_bytes(seg_bytes_len) + TM_WAVES * TM_MAX_LINE;
+}
+
+// ---- fused BERT-tiny kernel: fixed geometry --------------------------------
+constexpr int BF_WAVES = 8;
+constexpr int BF_S = 64;       // tokens per line
+constexpr int BF_H = 128;      // hidden
+constexpr int BF_HEADS = 2;
+constexpr int BF_DH = 64;      // head dim
+constexpr int BF_FFN = 512;
+constexpr int BF_VOCAB = 259;  // 256 byte values + pad/cls/unused
+constexpr int BF_NSTAMP = 22;  // timed variant: stamps per wave
+// Dynamic LDS of the fused kernel (x | Q,K / P+O / FFN-half | Vt | pooling).
+// bert_fused.hip static_asserts this against its private strides.
+constexpr int BF_LDS_BYTES = 72192;
+
+// bf16 weight blob (element offsets):
+//   tok_emb [VOCAB,H] | pos_emb [S,H] | n_layers x layer | w_score [H]
+// layer: wqkv_t [3H,H] | wo_t [H,H] | w1_t [FFN,H] | w2_t [H,FFN] |
+//        ln1_g | ln1_b | ln2_g | ln2_b  (each [H])
+constexpr int WB_TOK = 0;
+constexpr int WB_POS = WB_TOK + BF_VOCAB * BF_H;
+constexpr int WB_LAYER0 = WB_POS + BF_S * BF_H;
+constexpr int LW_QKV = 0;
+constexpr int LW_WO = LW_QKV + 3 * BF_H * BF_H;
+constexpr int LW_W1 = LW_WO + BF_H * BF_H;
+constexpr int LW_W2 = LW_W1 + BF_FFN * BF_H;
+constexpr int LW_LN1G = LW_W2 + BF_H * BF_FFN;
+constexpr int LW_LN1B = LW_LN1G + BF_H;
+constexpr int LW_LN2G = LW_LN1B + BF_H;
+constexpr int LW_LN2B = LW_LN2G + BF_H;
+constexpr int LW_SIZE = LW_LN2B + BF_H;
+// f32 bias blob: per layer [bqkv 3H | bo H | b1 FFN | b2 H], then b_score
+constexpr int FB_BQKV = 0;
+constexpr int FB_BO = FB_BQKV + 3 * BF_H;
+constexpr int FB_B1 = FB_BO + BF_H;
+constexpr int FB_B2 = FB_B1 + BF_FFN;
+constexpr int FB_SIZE = FB_B2 + BF_H;
+
+constexpr int64_t bert_fused_wb_elems(int n_layers) {
+  return WB_LAYER0 + (int64_t)n_layers * LW_SIZE + BF_H;
+}
+constexpr int64_t bert_fused_fb_elems(int n_layers) {
+  return (int64_t)n_layers * FB_SIZE + 1;
+}
+
+// ---- launchers --------------------------------------------------------------
+// Each enqueues on `stream` of the CURRENT device and does not synchronize.
+// The void ones report failure through hipGetLastError(); the fused-BERT
+// ones also set a per-(kernel, device) function attribute and can be
+// handed an unknown probe variant, so they return the error themselves.
+extern "C" {
+
+// gemm_bf16.hip
+void dmx_launch_fused_linear_bf16(const int16_t* A, const int16_t* Wt,
+                                  const float* bias, int16_t* C, int M, int N,
+                                  int K, int epilogue, hipStream_t stream);
+void dmx_launch_probe_mfma(const int16_t* A, const int16_t* B, float* D,
+                           int a_layout, int b_layout, hipStream_t stream);
+void dmx_launch_probe_mfma32(const int16_t* A, const int16_t* B, float* D,
+                             hipStream_t stream);
+
+// layernorm.hip (R and Xres may be null)
+void dmx_launch_layernorm_bf16(const int16_t* X, const int16_t* R,
+                               const int16_t* gamma, const int16_t* beta,
+                               int16_t* Y, int16_t* Xres, int M, int D,
+                               float eps, hipStream_t stream);
+
+// attention.hip, attention_mfma.hip
+void dmx_launch_attention_bf16(const int16_t* Q, const int16_t* K,
+                               const int16_t* V, int16_t* O, int BH, int S,
+                               int Dh, float scale, hipStream_t stream);
+void dmx_launch_attention_mfma_bf16(const int16_t* QKV, int16_t* O, int B,
+                                    int S, int H, int Dh, float scale,
+                                    hipStream_t stream);
+
+// bert_fused.hip
+hipError_t dmx_launch_bert_fused_bf16(const uint8_t* lines,
+                                      const int32_t* start, const int32_t* end,
+                                      const int16_t* wb, const float* fb,
+                                      float* scores, int B, int max_len,
+                                      int n_layers, float eps,
+                                      hipStream_t stream);
+// hipErrorInvalidValue when phase_mask names no compiled variant
+hipError_t dmx_launch_bert_fused_probe(const uint8_t* lines,
+                                       const int32_t* start,
+                                       const int32_t* end, const int16_t* wb,
+                                       const float* fb, float* scores, int B,
+                                       int max_len, int n_layers, float eps,
+                                       int phase_mask, hipStream_t stream);
+bool dmx_bert_fused_probe_mask_known(int phase_mask);
+// stamps: [B, BF_WAVES, BF_NSTAMP] u64 clock words
+hipError_t dmx_launch_bert_fused_timed(const uint8_t* lines,
+                                       const int32_t* start,
+                                       const int32_t* end, const int16_t* wb,
+                                       const float* fb, float* scores,
+                                       int64_t* stamps, int B, int max_len,
+                                       int n_layers, float eps,
+                                       hipStream_t stream);
+
+// template_match.hip (fmt_bytes / fmt_seg_off null when nf_seg == 0)
+void dmx_launch_template_match(
+    const uint8_t* lines, const int32_t* line_len, int B, int max_len,
+    const uint8_t* fmt_bytes, const int32_t* fmt_seg_off, int nf_seg,
+    const uint8_t* seg_bytes, int seg_bytes_len, const int32_t* seg_off,
+    const int32_t* tpl_seg_start, int n_tpl, int lower, int32_t* event_id,
+    int32_t* fmt_caps, int32_t* n_fmt_caps, int32_t* caps, int32_t* n_caps,
+    int32_t* span_start, int32_t* span_end, int max_fmt_caps, int max_caps,
+    hipStream_t stream);
+
+// hashset.hip (specs: [W, 4] int32 = kind, event, pos, pad)
+void dmx_launch_watch_hashes(const uint8_t* lines, int max_len,
+                             const int32_t* event_id, const int32_t* caps,
+                             const int32_t* n_caps, int max_caps,
+                             const int32_t* fmt_caps,
+                             const int32_t* n_fmt_caps, int max_fmt_caps,
+                             const int32_t* specs, int W, int B, int lower,
+                             int64_t* hashes, hipStream_t stream);
+void dmx_launch_hashset_insert(const int64_t* hashes, int64_t* tables, int B,
+                               int W, int capacity, hipStream_t stream);
+void dmx_launch_hashset_probe(const int64_t* hashes, const int64_t* tables,
+                              int B, int W, int capacity, int32_t* unseen,
+                              hipStream_t stream);
+
+// edit_distance.hip
+void dmx_launch_edit_distance(const uint8_t* A, const int32_t* a_len, int Na,
+                              const uint8_t* B, const int32_t* b_len, int Nb,
+                              int max_len, int32_t* dist, hipStream_t stream);
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 // reductions, fused residual add so the row is read once (HBM3E-bound
 // ops get fused into the producing pass — SURVEY.md build mandate).
 #include "common.h"
+#include "kernels.h"
 
 extern "C" __global__ __launch_bounds__(256)
 void dmx_layernorm_bf16(
@@ -147,8 +148,9 @@ __global__ __launch_bounds__(256) void dmx_layernorm_rowgroup_bf16(
 }
 
 extern "C" void dmx_launch_layernorm_bf16(
-    const void* X, const void* R, const void* gamma, const void* beta,
-    void* Y, void* Xres, int M, int D, float eps, hipStream_t stream) {
+    const int16_t* X, const int16_t* R, const int16_t* gamma,
+    const int16_t* beta, int16_t* Y, int16_t* Xres, int M, int D, float eps,
+    hipStream_t stream) {
   // Row-group fast path for D in {64, 128, 256, 512}.
   const int lpr = D / 8;
   if (D == 64 || D == 128 || D == 256 || D == 512) {
@@ -157,37 +159,28 @@ extern "C" void dmx_launch_layernorm_bf16(
     switch (D) {
       case 64:
         hipLaunchKernelGGL(dmx_layernorm_rowgroup_bf16<8>, dim3(grid),
-                           dim3(256), 0, stream, (const short*)X,
-                           (const short*)R, (const short*)gamma,
-                           (const short*)beta, (short*)Y, (short*)Xres, M, D,
-                           eps);
+                           dim3(256), 0, stream, X, R, gamma, beta, Y, Xres,
+                           M, D, eps);
         return;
       case 128:
         hipLaunchKernelGGL(dmx_layernorm_rowgroup_bf16<16>, dim3(grid),
-                           dim3(256), 0, stream, (const short*)X,
-                           (const short*)R, (const short*)gamma,
-                           (const short*)beta, (short*)Y, (short*)Xres, M, D,
-                           eps);
+                           dim3(256), 0, stream, X, R, gamma, beta, Y, Xres,
+                           M, D, eps);
         return;
       case 256:
         hipLaunchKernelGGL(dmx_layernorm_rowgroup_bf16<32>, dim3(grid),
-                           dim3(256), 0, stream, (const short*)X,
-                           (const short*)R, (const short*)gamma,
-                           (const short*)beta, (short*)Y, (short*)Xres, M, D,
-                           eps);
+                           dim3(256), 0, stream, X, R, gamma, beta, Y, Xres,
+                           M, D, eps);
         return;
       case 512:
         hipLaunchKernelGGL(dmx_layernorm_rowgroup_bf16<64>, dim3(grid),
-                           dim3(256), 0, stream, (const short*)X,
-                           (const short*)R, (const short*)gamma,
-                           (const short*)beta, (short*)Y, (short*)Xres, M, D,
-                           eps);
+                           dim3(256), 0, stream, X, R, gamma, beta, Y, Xres,
+                           M, D, eps);
         return;
     }
   }
   const int waves_per_block = 256 / DMX_WAVE;
   const int grid = (M + waves_per_block - 1) / waves_per_block;
   hipLaunchKernelGGL(dmx_layernorm_bf16, dim3(grid), dim3(256), 0, stream,
-                     (const short*)X, (const short*)R, (const short*)gamma,
-                     (const short*)beta, (short*)Y, (short*)Xres, M, D, eps);
+                     X, R, gamma, beta, Y, Xres, M, D, eps);
 }

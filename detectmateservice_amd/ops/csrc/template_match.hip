@@ -16,9 +16,7 @@
 // wave-parallel: 64 candidate start positions per step, first match via
 // __ballot (64-bit on CDNA) + ffs.
 #include "common.h"
-
-#define TM_WAVES 4
-#define TM_MAX_LINE 512
+#include "kernels.h"  // TM_WAVES, TM_MAX_LINE, tm_lds_bytes
 
 // Wave-parallel find of seg[0..sl) in line_lds[pos..limit): returns first
 // index or -1; uniform across the wave (ballot is wave-uniform).
@@ -113,7 +111,7 @@ void dmx_template_match(
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* seg_lds = smem;                       // [seg_bytes_len]
-  unsigned char* line_lds = smem + ((seg_bytes_len + 15) & ~15)
+  unsigned char* line_lds = smem + tm_seg_lds_bytes(seg_bytes_len)
                             + wid * TM_MAX_LINE;       // per-wave line
 
   // stage segment blob once per block (all threads cooperate)
@@ -176,23 +174,19 @@ void dmx_template_match(
 }
 
 extern "C" void dmx_launch_template_match(
-    const void* lines, const void* line_len, int B, int max_len,
-    const void* fmt_bytes, const void* fmt_seg_off, int nf_seg,
-    const void* seg_bytes, int seg_bytes_len, const void* seg_off,
-    const void* tpl_seg_start, int n_tpl, int lower,
-    void* event_id, void* fmt_caps, void* n_fmt_caps, void* caps,
-    void* n_caps, void* span_start, void* span_end, int max_fmt_caps,
-    int max_caps, hipStream_t stream) {
+    const uint8_t* lines, const int32_t* line_len, int B, int max_len,
+    const uint8_t* fmt_bytes, const int32_t* fmt_seg_off, int nf_seg,
+    const uint8_t* seg_bytes, int seg_bytes_len, const int32_t* seg_off,
+    const int32_t* tpl_seg_start, int n_tpl, int lower, int32_t* event_id,
+    int32_t* fmt_caps, int32_t* n_fmt_caps, int32_t* caps, int32_t* n_caps,
+    int32_t* span_start, int32_t* span_end, int max_fmt_caps, int max_caps,
+    hipStream_t stream) {
   const int grid = (B + TM_WAVES - 1) / TM_WAVES;
-  const size_t lds = ((seg_bytes_len + 15) & ~15) + TM_WAVES * TM_MAX_LINE;
+  // the caller keeps this within LDS_DEFAULT_LIMIT (no opt-in attribute)
   hipLaunchKernelGGL(dmx_template_match, dim3(grid), dim3(TM_WAVES * DMX_WAVE),
-                     lds, stream,
-                     (const unsigned char*)lines, (const int*)line_len, B,
-                     max_len, (const unsigned char*)fmt_bytes,
-                     (const int*)fmt_seg_off, nf_seg,
-                     (const unsigned char*)seg_bytes, seg_bytes_len,
-                     (const int*)seg_off, (const int*)tpl_seg_start, n_tpl,
-                     lower, (int*)event_id, (int*)fmt_caps, (int*)n_fmt_caps,
-                     (int*)caps, (int*)n_caps, (int*)span_start,
-                     (int*)span_end, max_fmt_caps, max_caps);
+                     tm_lds_bytes(seg_bytes_len), stream, lines, line_len, B,
+                     max_len, fmt_bytes, fmt_seg_off, nf_seg, seg_bytes,
+                     seg_bytes_len, seg_off, tpl_seg_start, n_tpl, lower,
+                     event_id, fmt_caps, n_fmt_caps, caps, n_caps, span_start,
+                     span_end, max_fmt_caps, max_caps);
 }

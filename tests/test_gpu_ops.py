@@ -251,6 +251,29 @@ def test_attention_qkv_mfma_s32():
     assert (o - ref).abs().max() < 0.03
 
 
+@pytest.mark.parametrize("B,S,H,Dh", [(2, 96, 2, 32), (2, 128, 1, 64)])
+def test_attention_qkv_mfma_more_than_one_tile_per_wave(B, S, H, Dh):
+    """S > 64: the 4 waves each own more than one 16-row query tile. Every
+    one of the S output rows must be computed (the output is allocated
+    uninitialised), against the same CPU fp32 softmax reference and
+    tolerance as test_attention_qkv_mfma_vs_reference."""
+    from detectmateservice_amd import ops
+
+    torch.manual_seed(7)
+    qkv = (torch.randn(B, S, 3 * H * Dh) * 0.5).bfloat16().cuda()
+    o = ops.attention_qkv(qkv, S, H, Dh).float().cpu()
+    q, k, v = qkv.float().cpu().view(B, S, 3, H, Dh).unbind(dim=2)
+    q = q.permute(0, 2, 1, 3)
+    k = k.permute(0, 2, 1, 3)
+    v = v.permute(0, 2, 1, 3)
+    s = torch.softmax(q @ k.transpose(-1, -2) / Dh ** 0.5, -1)
+    ref = (s @ v).permute(0, 2, 1, 3).reshape(B, S, H * Dh)
+    assert o.shape == ref.shape
+    err = (o - ref).abs().amax(dim=(0, 2))  # per query row
+    assert torch.isfinite(o).all()
+    assert err.max() < 0.03, (int(err.argmax()), float(err.max()))
+
+
 def test_bert_fused_vs_layered():
     """Fused whole-model kernel vs the layered GPU path (same weights)."""
     from detectmateservice_amd import ops
