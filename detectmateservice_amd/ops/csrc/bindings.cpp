@@ -245,6 +245,11 @@ DeviceScope check_bert_fused_args(const torch::Tensor& lines,
   check_arg(fb, "fb", torch::kFloat32, 1);
   check_numel(fb, "fb", bert_fused_fb_elems((int)n_layers),
               "bert_fused_fb_elems(n_layers)");
+  // the kernel fetches four biases with one 16-byte load (a storage-offset
+  // view of a larger tensor can be contiguous and still start mid-vector)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(fb.data_ptr<float>()) % 16 == 0,
+              "fb: bias blob must be 16-byte aligned, got storage offset ",
+              fb.storage_offset(), " floats");
   return DeviceScope(
       {{"lines", lines}, {"start", start}, {"end", end}, {"wb", wb}, {"fb", fb}});
 }

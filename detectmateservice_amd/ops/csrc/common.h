@@ -50,9 +50,19 @@ static __device__ __forceinline__ float gelu_f32(float x) {
   // computable with ONE v_exp + one reciprocal instead of libm tanhf
   // (branchy, multiple transcendentals — it made the FFN phase half the
   // fused kernel's per-wave work, tools/probe_bert_timing.py).
-  const float two_c = 1.5957691216057308f;  // 2*sqrt(2/pi)
-  const float z = two_c * (x + 0.044715f * x * x * x);
-  return x / (1.0f + __expf(-z));
+  //
+  // exp(-z) = exp2(x * (k1 + k2 x^2)) with -log2(e) folded into both
+  // constants, so the exponent feeds the native base-2 v_exp_f32, and the
+  // IEEE division (v_div_scale x2, v_div_fmas, v_div_fixup and a Newton
+  // chain: ~9 of the ~20 VALU ops per element) becomes one v_rcp_f32
+  // (1 ulp). Seven VALU ops: mul, fma, mul, exp, add, rcp, mul. The result
+  // is rounded to bf16 by every caller, far above the 1-ulp difference.
+  // Extremes: x << 0 -> exp2 = +inf -> rcp = 0 -> x*0 = -0;
+  // x >> 0 -> exp2 = 0 -> x*1 = x; no NaN for any finite x.
+  const float k1 = -2.3022082f;    // -log2(e) * 2*sqrt(2/pi)
+  const float k2 = -0.10294324f;   // k1 * 0.044715
+  const float u = x * __builtin_fmaf(x * x, k2, k1);
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u));
 }
 
 static __device__ __forceinline__ float warp_reduce_sum_f32(float v) {
