@@ -2,94 +2,103 @@
 //
 // The flagship detector config (BASELINE.json config 5) is tiny enough
 // that the idiomatic MI355X mapping is a per-line megakernel: all
-// activations for one line (S=64 tokens, hidden 128) live in LDS for the
-// whole forward pass; the model's weights (~600 KB) are read through the
-// XCD L2s and shared by every workgroup; HBM traffic is line bytes in +
-// one f32 score out.
+// activations for one line live in LDS for the whole forward pass; the
+// model's weights (~600 KB) are read through the XCD L2s and shared by
+// every workgroup; HBM traffic is line bytes in + one f32 score out.
 //
-// v3 design notes (PMC-driven, profiles/*):
-//  * v1 (layered kernels) was HBM-bound on inter-op traffic (74% GEMM).
-//  * v2 (fused, 118 KiB arena, 1 block/CU) showed MemUnitStalled~0 and
-//    VALUBusy 33%: bulk-synchronous phases at 1 block/CU leave the CU
-//    idle at every barrier. This version shrinks the arena to ~70 KiB so
-//    TWO blocks co-reside per CU - one block's barrier idle overlaps the
-//    other block's compute. 8 waves/block (512 thr), VGPR<=128 keeps both
-//    resident (4 waves/SIMD from two independent barrier domains).
-//  * arena cuts: qkv buffer holds Q|K only (V written transposed to vt
-//    during the qkv GEMM epilogue); FFN runs in two K=256 halves that
-//    accumulate into x; the attention P tile aliases the (dead) Q|K area.
-//  * pair-chunked weight fragments: one L2 B-fragment load feeds two
-//    independent MFMA chains.
+// Geometry (kernels.h, checked by the bindings): S=64 tokens, H=128,
+// 2 heads (Dh=64), FFN=512, any layer count. 8 waves x 64 lanes.
 //
-// v4: epilogue / softmax instruction diet (profiles/r14). The kernel is
-// instruction-issue-bound at 4 waves/SIMD, and most of the issue was not
-// MFMA: the W1 GEMM carried 686 other vector instructions around 32 MFMAs.
-//  * gelu_f32 (common.h): hardware reciprocal + base-2 exp instead of the
-//    IEEE division expansion (-7.1% step time on its own).
-//  * operand-swapped MFMA, mfma(weight, activation): the lane owns one row
-//    and FOUR CONSECUTIVE columns, so every row-major epilogue is one
-//    8-byte LDS store (and one 8-byte residual load) per fragment instead
-//    of four 2-byte ones, and the bias is one 16-byte load that seeds the
-//    accumulators. The qkv GEMM picks swapped (Q|K) or plain (V, written
-//    transposed) once per wave on a scalar (-8.2%).
-//  * attention the same way: S^T and O^T tiles put a whole query in the
-//    lanes lane&15, so softmax reductions are in-lane plus two cross-lane
-//    steps, 1/sum is already where it is used, P and O leave as 8-byte
-//    stores (-4.8%).
-//  * the adjacent values invite v_pk_mul_f32 / v_pk_add_f32 (16 in W1, 8
-//    per residual GEMM). Keeping them apart needs inline-asm arithmetic,
-//    which steps outside the compiler's hazard handling (a v_rcp_f32
-//    result read too early) and computed garbage: not done (r14).
+// Two blocks per CU. The phases are bulk-synchronous, so a lone block
+// leaves its CU idle at every barrier; with a ~70 KiB arena and <= 128
+// VGPRs two blocks co-reside (4 waves/SIMD from two independent barrier
+// domains) and one block's barrier wait overlaps the other's compute.
 //
-// Fixed geometry (asserted host-side): S=64 tokens, H=128, 2 heads
-// (Dh=64), FFN=512, arbitrary layer count.
+// Arena (the Tile aliases below): x | buf | vt, bf16, then [H] f32 for
+// pooling. `buf` has three tenants in turn: Q|K; then the per-wave P tiles
+// followed by the attention output; then one FFN half. V never enters buf:
+// the qkv GEMM writes it transposed into vt, k-contiguous for the P.V MFMA.
+//
+// Schedule (bert_fused_body; every `|` is a block barrier):
+//   embed | per layer: qkv | attention (one barrier inside, before the P
+//   tiles overwrite Q|K) | x += Wo | LN1 | 2 x (W1 half + GELU | x += W2
+//   half |) LN2 | pool | score.
+//
+// Operand order. The 16x16x32 bf16 A and B fragment layouts are the same
+// function of the lane (row or column lane&15, k (lane>>4)*8..+7), so
+// mfma(weight, activation) yields the transposed tile of mfma(activation,
+// weight): the lane then owns ONE row m = fm*16 + (lane&15) and FOUR
+// CONSECUTIVE columns n = fn*16 + (lane>>4)*4 + r. Everything stored
+// row-major runs weight-first: the four results leave as one 8-byte LDS
+// store, a residual arrives as one 8-byte load, the bias as one 16-byte
+// load. Only V keeps activation-first order: there the lane owns four
+// consecutive m of one n, which is what is contiguous in vt[n][m..m+3].
+// Attention does the same with S^T = K Q^T and O^T = V^T P^T.
+//
+// The adjacent values invite v_pk_mul_f32 / v_pk_add_f32 in the epilogues,
+// an anti-lever beside MFMAs. The compiler's pairing is left alone: keeping
+// them apart needs inline-asm arithmetic, which steps outside the
+// compiler's hazard handling (a v_rcp_f32 result read too early) and
+// computed garbage.
 #include "common.h"
 #include "kernels.h"  // geometry, blob offsets, BF_LDS_BYTES, launchers
 
-// Explicit LDS address-space typing: the noinline block_gemm receives the
-// arena pointers as arguments, and a generic (flat) short* there makes
-// hipcc emit flat_load for what are really LDS reads (35 flat_load in the
-// .s before this change). AS(3) pointers guarantee ds_* lowering.
+// Explicit address-space typing: a generic (flat) short* makes hipcc emit
+// flat_load for what are really LDS reads. AS(3) pointers guarantee ds_*
+// lowering.
 typedef __attribute__((address_space(3))) short lds_short;
+typedef __attribute__((address_space(3))) short4v lds_short4;
+typedef __attribute__((address_space(3))) float lds_float;
 typedef __attribute__((address_space(1))) const short glob_cshort;
 typedef __attribute__((address_space(1))) const float glob_cfloat;
-typedef __attribute__((address_space(3))) const short lds_cshort;
-typedef __attribute__((address_space(3))) float lds_float;
 
 #define BF_THREADS (BF_WAVES * DMX_WAVE)
 
 // LDS strides (elements); +8 pads keep rows 16-B aligned and bank-spread
-#define XS (BF_H + 8)       // 136, x rows
-// QKS at +16 (not +8): stride 136 dw = 8 mod 64 makes the FFN W2 /
-// attention A-fragment ds_read_b128 groups conflict-free (PMC: FFN's
-// 6.98B conflict cycles are 100% A-reads — probe ABL=2 zeroes them).
-// Q|K (64x272=17408) and FFN halves still fit inside BUF_ELEMS (17920,
-// sized by the P+O region), so this costs ZERO extra LDS. Measured
-// NEUTRAL on wall (7.30M both ways): in this latency-bound regime the
-// conflict cycles hide under the operand waits — kept because it is
-// free and removes them from every future profile.
+#define XS (BF_H + 8)  // 136, x and attention-output rows
+// QKS at +16 (not +8): stride 136 dw = 8 mod 64 makes the W2 / attention
+// A-fragment ds_read_b128 groups conflict-free. Both tenants still fit in
+// buf (asserted below), so it costs no LDS.
 #define QKS (2 * BF_H + 16)  // 272, Q|K rows and FFN-half rows
-#define VTS (BF_S + 8)      // 72, transposed-V and P rows
-#define O_OFF (BF_WAVES * 16 * VTS)    // 9216: attn-out after the P tiles
-#define BUF_ELEMS (O_OFF + BF_S * XS)  // 17920 = P+O (>= QK 17408)
+#define VTS (BF_S + 8)       // 72, transposed-V and P rows
 
-// arena: x [S][XS] | buf | Vt [2*Dh][VTS] (bf16), then [H] f32 pooling
-static_assert(BF_LDS_BYTES ==
-                  (BF_S * XS + BUF_ELEMS + 2 * BF_DH * VTS) * sizeof(short) +
-                      BF_H * sizeof(float),
+// ---- LDS arena --------------------------------------------------------------
+extern __shared__ __attribute__((aligned(16))) short smem_raw[];
+
+// A [ROWS][COLS] bf16 tenant of the arena: OFF elements from its base, rows
+// STRIDE apart.
+template <int OFF_, int ROWS, int COLS_, int STRIDE_>
+struct Tile {
+  static constexpr int OFF = OFF_, COLS = COLS_, STRIDE = STRIDE_;
+  static constexpr int END = OFF + ROWS * STRIDE;
+  // The GEMM and attention epilogues move four bf16 per lane with one
+  // 8-byte LDS access at column offsets that are multiples of 4.
+  static_assert(OFF % 4 == 0 && STRIDE % 4 == 0 && COLS <= STRIDE,
+                "8-byte LDS access: offsets and strides are multiples of 4");
+  static __device__ __forceinline__ lds_short* ptr() {
+    return (lds_short*)smem_raw + OFF;
+  }
+};
+using XTile = Tile<0, BF_S, BF_H, XS>;
+// buf, first tenant
+using QkTile = Tile<XTile::END, BF_S, 2 * BF_H, QKS>;
+// buf, second tenants: wave w owns P rows 16w .. 16w+15
+using PTiles = Tile<XTile::END, BF_WAVES * 16, BF_S, VTS>;
+using AttnOut = Tile<PTiles::END, BF_S, BF_H, XS>;
+// buf, third tenant
+using FfnHalf = Tile<XTile::END, BF_S, BF_FFN / 2, QKS>;
+using VtTile = Tile<AttnOut::END, 2 * BF_DH, BF_S, VTS>;  // after buf
+constexpr int RED_OFF = VtTile::END;                      // [H] f32 pooling
+
+static_assert(QkTile::END <= VtTile::OFF, "Q|K runs past buf");
+static_assert(FfnHalf::END <= VtTile::OFF, "the FFN half runs past buf");
+static_assert(PTiles::END <= AttnOut::OFF,
+              "the P tiles reach into the attention output");
+static_assert(AttnOut::END <= VtTile::OFF,
+              "the attention output runs past buf");
+static_assert(BF_LDS_BYTES == RED_OFF * sizeof(short) + BF_H * sizeof(float),
               "kernels.h BF_LDS_BYTES out of step with the LDS strides");
-
-// The GEMM and attention epilogues move four bf16 per lane with one 8-byte
-// LDS access at column offsets that are multiples of 4, so every row
-// stride and every region offset they are used with must be a multiple of
-// 4 elements (the arena base is 16-byte aligned).
-static_assert(XS % 4 == 0 && QKS % 4 == 0 && VTS % 4 == 0,
-              "8-byte LDS access: row strides must be multiples of 4");
-static_assert(O_OFF % 4 == 0 && (BF_S * XS) % 4 == 0 && BUF_ELEMS % 4 == 0 &&
-                  (BF_WAVES * 16 * VTS) % 4 == 0 && (16 * VTS) % 4 == 0,
-              "8-byte LDS access: buf, vt, P-tile and O offsets must be "
-              "multiples of 4");
-// ... and the swapped GEMMs fetch four biases with one 16-byte load: every
+// The weight-first GEMMs fetch four biases with one 16-byte load: every
 // bias vector must start a multiple of 4 floats into the (16-byte aligned,
 // checked by the bindings) blob.
 static_assert(FB_BQKV % 4 == 0 && FB_BO % 4 == 0 && FB_B1 % 4 == 0 &&
@@ -97,7 +106,33 @@ static_assert(FB_BQKV % 4 == 0 && FB_BO % 4 == 0 && FB_B1 % 4 == 0 &&
                   (BF_FFN / 2) % 4 == 0,
               "16-byte bias loads: bias offsets must be multiples of 4");
 
-typedef __attribute__((address_space(3))) short4v lds_short4;
+// ---- MFMA fragment addressing in LDS --------------------------------------
+// A lane's place in every 16x16 fragment: l15 = lane&15, l4 = lane>>4. Each
+// phase splits the lane once and hands the pair to the helpers below.
+struct FragLane {
+  int l15, l4;
+  __device__ __forceinline__ explicit FragLane(int lane)
+      : l15(lane & 15), l4(lane >> 4) {}
+};
+
+// 16x16x32 bf16 operand fragment (A and B alike) whose first row is r0 and
+// first k is k0: the lane reads row r0 + l15, k0 + l4*8 .. +7, one
+// ds_read_b128.
+static __device__ __forceinline__ bf16x8 lds_frag(const lds_short* base,
+                                                  int stride, int r0, int k0,
+                                                  FragLane fl) {
+  return *(const __attribute__((address_space(3))) bf16x8*)(
+      base + (r0 + fl.l15) * stride + k0 + fl.l4 * 8);
+}
+
+// The four consecutive elements a lane owns of the 16x16 accumulator tile at
+// (r0, c0): row r0 + l15, columns c0 + l4*4 .. +3, one 8-byte LDS access
+// either way.
+static __device__ __forceinline__ lds_short4* lds_quad(lds_short* base,
+                                                       int stride, int r0,
+                                                       int c0, FragLane fl) {
+  return (lds_short4*)(base + (r0 + fl.l15) * stride + c0 + fl.l4 * 4);
+}
 
 // four f32 -> four bf16 (RNE, as f32_to_bf16) as two v_cvt_pk_bf16_f32;
 // element-wise f32_to_bf16 left the compiler re-pairing halves with
@@ -114,25 +149,24 @@ static __device__ __forceinline__ short4v pack_bf16x4(f32x4 v) {
 // bit 1 = B operand from an opaque register instead of the L2 weight
 // load (removes vmcnt parks); bit 2 = A operand from a register instead
 // of the LDS read (removes lgkmcnt parks). Epilogue stores stay, so the
-// MFMA chains cannot be dead-code-eliminated (guide §5.4 rule 17).
-// All pointers __restrict__: without it the epilogue's LDS stores
-// between quads alias the activation reads for the analyzer (the
-// pointers arrive as opaque noinline args), so the compiler re-reads
-// every A fragment per quad (32 ds_reads for 32 MFMAs in the .s) and
-// cannot hoist reads across the quad boundary. The caller guarantees
-// in_lds never overlaps this GEMM's outputs.
+// MFMA chains cannot be dead-code-eliminated.
+// All pointers __restrict__: the pointers arrive as opaque noinline
+// arguments, and without it the epilogue's LDS stores between quads alias
+// the activation reads for the analyzer, which then re-reads every A
+// fragment per quad and cannot hoist reads across the quad boundary. The
+// caller guarantees in_lds never overlaps this GEMM's outputs.
 //
-// Operand order (SWAP). The 16x16x32 bf16 A and B fragment layouts are the
-// same function of the lane (row or column lane&15, k (lane>>4)*8..+7), so
-// mfma(weight, activation) yields the transposed tile of mfma(activation,
-// weight): the lane then owns ONE row m = fm*16 + (lane&15) and FOUR
-// CONSECUTIVE columns n0 = fn*16 + (lane>>4)*4 + r. Row-major outputs
-// (MODE 0, MODE 2, the Q|K columns of MODE 1) run swapped: the bias is one
-// 16-byte load that seeds the accumulators (no epilogue add), the four
-// results leave as one 8-byte LDS store (was four 2-byte stores), and the
-// MODE 2 residual arrives as one 8-byte LDS load. The V columns of MODE 1
-// keep weight-as-B order: there the lane owns four consecutive m of one n,
-// which is what is contiguous in vt[n][m..m+3].
+// SWAP is the weight-first operand order of the file header: MODE 0, MODE 2
+// and the Q|K columns of MODE 1 run swapped, the V columns of MODE 1 do not.
+//
+// The three functions below keep one scalar argument list and spell their
+// fragment addresses out instead of using lds_frag / lds_quad. Every call
+// passes the same LDS addresses and strides, the compiler folds them into
+// each block_gemm instance, and the code it then generates depends on how
+// they arrive: bundled into by-value structs, turned into compile-time
+// tiles, or merely read through lds_frag, the qkv GEMM comes out between
+// 719 and 806 instructions instead of 741 and spills up to 13 more
+// registers (profiles/r15_fused_refactor_isa.txt).
 template <int K, int MODE, int ACT, int WTS, int ABL, bool BIAS, bool SWAP>
 static __device__ __forceinline__ void gemm_quad(
     const lds_short* __restrict__ in_lds, int in_stride,
@@ -210,9 +244,7 @@ static __device__ __forceinline__ void gemm_quad(
 
 // CNT consecutive quads from fn0, all in one operand order. unroll 2: the
 // second quad's (independent) weight loads issue under the first quad's
-// MFMA chains, hiding the L2 latency that dominated the per-quad cost
-// (phase probe: GEMMs ~3.9 of 4.5 ms while pure MFMA issue accounts for
-// <10% of that)
+// MFMA chains, hiding the L2 latency that dominates the per-quad cost
 template <int K, int MODE, int ACT, int WTS, int ABL, bool BIAS, bool SWAP,
           int CNT>
 static __device__ __forceinline__ void gemm_quads(
@@ -286,11 +318,108 @@ static __device__ __attribute__((noinline)) void block_gemm(
   }
 }
 
+// ---- embed: x[s][c] = tok_emb[byte+3 or 0][c] + pos_emb[s][c] -------------
+static __device__ __forceinline__ void embed(
+    const unsigned char* __restrict__ lines, const int* __restrict__ start,
+    const int* __restrict__ end, const short* __restrict__ wb, lds_short* x_lds,
+    int line, int max_len, int tid) {
+  const int s0 = start[line], e0 = end[line];
+  for (int i = tid * 8; i < BF_S * BF_H; i += BF_THREADS * 8) {
+    const int s = i / BF_H, c = i % BF_H;
+    int tok = 0;
+    const int idx = s0 + s;
+    if (idx < e0 && idx < max_len)
+      tok = (int)lines[(long)line * max_len + idx] + 3;
+    short8v te = *(const short8v*)(wb + WB_TOK + (long)tok * BF_H + c);
+    short8v pe = *(const short8v*)(wb + WB_POS + (long)s * BF_H + c);
+    short8v xv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      xv[j] = f32_to_bf16(bf16_to_f32(te[j]) + bf16_to_f32(pe[j]));
+    *(__attribute__((address_space(3))) short8v*)(x_lds + s * XS + c) = xv;
+  }
+}
+
+// ---- attention: wave = (head hh, 16 q-rows) -------------------------------
+// Both MFMAs run weight-first (file header): S^T = K Q^T puts query
+// q0 + (lane&15) and 16 keys (f*16 + (lane>>4)*4 + r) in each lane, so a
+// softmax row is 15 in-lane ops plus two cross-lane steps (xor 16, 32),
+// every lane of a query ends up holding that query's 1/sum, and P leaves as
+// four 8-byte stores. O^T = V^T P^T again gives the lane its own query and
+// four consecutive d: scaled by the in-lane 1/sum (no __shfl) and stored
+// 8 bytes at a time.
+static __device__ __forceinline__ void attention(int wid, int lane) {
+  const FragLane fl(lane);
+  const int hh = wid >> 2;
+  const int q0 = (wid & 3) * 16;
+  const float scale = 0.125f;  // 1/sqrt(64)
+
+  f32x4 acc_p[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) acc_p[f] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < BF_DH / 32; ++ks) {
+    bf16x8 qf = lds_frag(QkTile::ptr(), QKS, q0, hh * BF_DH + ks * 32, fl);
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+      acc_p[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          lds_frag(QkTile::ptr(), QKS, f * 16, BF_H + hh * BF_DH + ks * 32, fl),
+          qf, acc_p[f], 0, 0, 0);
+  }
+  float m = -1e30f;
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m = fmaxf(m, acc_p[f][r] * scale);
+  m = fmaxf(m, __shfl_xor(m, 16, 64));
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float e = __expf(acc_p[f][r] * scale - m);
+      acc_p[f][r] = e;
+      sum += e;
+    }
+  sum += __shfl_xor(sum, 16, 64);
+  sum += __shfl_xor(sum, 32, 64);
+  const float inv = 1.f / sum;
+  // P tiles alias the Q|K area: every wave must be done reading Q/K
+  __syncthreads();
+  lds_short* my_p = PTiles::ptr() + wid * 16 * VTS;
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+    *lds_quad(my_p, VTS, 0, f * 16, fl) = pack_bf16x4(acc_p[f]);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-local P
+
+  f32x4 acc_o[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) acc_o[f] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < BF_S / 32; ++ks) {
+    bf16x8 pf = lds_frag(my_p, VTS, 0, ks * 32, fl);
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+      acc_o[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          lds_frag(VtTile::ptr(), VTS, hh * BF_DH + f * 16, ks * 32, fl), pf,
+          acc_o[f], 0, 0, 0);
+  }
+  // out[q][hh*64 + d], disjoint from the P tiles (asserted at the tiles)
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    f32x4 o = acc_o[f];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] *= inv;
+    *lds_quad(AttnOut::ptr(), XS, q0, hh * BF_DH + f * 16, fl) = pack_bf16x4(o);
+  }
+}
+
 // ---- in-block LayerNorm on x (post-LN) -----------------------------------
 // All 8 of the wave's rows in ONE parallel pass: 8 lanes per row, 16
 // elements per lane, 3-step shfl_xor reduction within each 8-lane row
-// group. (The serial per-row loop with full-wave reductions measured
-// +1.12 ms of the 5.2 ms step — as costly as the whole QKV GEMM.)
+// group (a serial per-row loop with full-wave reductions costs as much as
+// the whole qkv GEMM).
 static __device__ __forceinline__ void block_layernorm(
     lds_short* x_lds, const short* __restrict__ gamma,
     const short* __restrict__ beta, int wid, int lane, float eps) {
@@ -334,6 +463,27 @@ static __device__ __forceinline__ void block_layernorm(
   *(__attribute__((address_space(3))) short8v*)(x_lds + row * XS + c0 + 8) = ob;
 }
 
+// ---- pool (mean over S) + score head --------------------------------------
+static __device__ __forceinline__ void pool_score(
+    const short* __restrict__ w_score, const float* __restrict__ b_score,
+    float* __restrict__ score, int tid) {
+  const lds_short* x_lds = XTile::ptr();
+  lds_float* red = (lds_float*)((lds_short*)smem_raw + RED_OFF);
+  if (tid < BF_H) {
+    float s = 0.f;
+    for (int row = 0; row < BF_S; ++row)
+      s += bf16_to_f32(x_lds[row * XS + tid]);
+    red[tid] = (s / BF_S) * bf16_to_f32(w_score[tid]);
+  }
+  __syncthreads();
+  const int wid = tid / DMX_WAVE, lane = tid % DMX_WAVE;
+  if (wid == 0) {
+    float v = red[lane] + red[lane + 64];
+    v = warp_reduce_sum_f32(v);
+    if (lane == 0) *score = v + *b_score;
+  }
+}
+
 // Phase bits for the profiling probe (production uses PH_ALL; skipped
 // phases cannot be dead-code-eliminated backwards because every phase
 // ends in LDS stores).
@@ -344,11 +494,35 @@ static __device__ __forceinline__ void block_layernorm(
 #define PH_FFN 16
 #define PH_ALL 31
 
-// Per-wave phase timing (diagnostic builds): stamps[k] = s_memrealtime at
-// phase boundaries; slot pairs (work-done, barrier-crossed) separate each
-// wave's compute time from its barrier wait. 100 MHz constant clock.
-// BF_NSTAMP slots per wave (kernels.h).
+// Per-wave phase timing (diagnostic builds): mark() stores s_memrealtime
+// (100 MHz constant clock) at each phase boundary; slot pairs (work-done,
+// barrier-crossed) separate a wave's compute time from its barrier wait.
+// BF_NSTAMP slots per wave (kernels.h); unused ones are flushed as 0.
+// Empty, and free, when not TIMED.
+template <bool TIMED>
+struct StampRecorder {
+  __device__ void mark() {}
+  __device__ void flush(unsigned long long*, int, int, int) {}
+};
+template <>
+struct StampRecorder<true> {
+  unsigned long long t[BF_NSTAMP];
+  int n = 0;
+  __device__ void mark() {
+    if (n < BF_NSTAMP) t[n++] = __builtin_amdgcn_s_memrealtime();
+  }
+  // out: [B, BF_WAVES, BF_NSTAMP]
+  __device__ void flush(unsigned long long* out, int line, int wid, int lane) {
+    if (lane == 0 && out != nullptr) {
+      unsigned long long* dst = out + ((long)line * BF_WAVES + wid) * BF_NSTAMP;
+      for (int k = 0; k < BF_NSTAMP; ++k) dst[k] = k < n ? t[k] : 0ull;
+    }
+  }
+};
 
+// The schedule: phase, stamp, barrier, stamp. Stamp slots: 0 kernel start,
+// 1-2 embed, then per layer (work done, barrier crossed) for qkv,
+// attention, proj+LN1 and ffn+LN2, and one final stamp.
 template <int PHASES, bool TIMED = false, int ABL = 0>
 static __device__ __forceinline__ void bert_fused_body(
     const unsigned char* __restrict__ lines,  // [B, max_len]
@@ -359,168 +533,57 @@ static __device__ __forceinline__ void bert_fused_body(
     float* __restrict__ scores,               // [B]
     int B, int max_len, int n_layers, float eps,
     unsigned long long* __restrict__ stamps_out = nullptr) {
-  unsigned long long tstamp[TIMED ? BF_NSTAMP : 1];
-  int tidx = 0;
-#define BF_STAMP()                                                          \
-  if constexpr (TIMED) {                                                    \
-    if (tidx < BF_NSTAMP) tstamp[tidx++] = __builtin_amdgcn_s_memrealtime(); \
-  }
+  StampRecorder<TIMED> stamp;
   const int line = blockIdx.x;
   if (line >= B) return;
   const int tid = threadIdx.x;
   const int wid = tid / DMX_WAVE;
   const int lane = tid % DMX_WAVE;
 
-  extern __shared__ __attribute__((aligned(16))) short smem_raw[];
-  lds_short* smem = (lds_short*)smem_raw;
-  lds_short* x_lds = smem;             // [64][XS]
-  lds_short* buf = x_lds + BF_S * XS;  // BUF_ELEMS: QK | P+O | FFN-half
-  lds_short* vt = buf + BUF_ELEMS;     // [128][VTS]
-  lds_float* red = (lds_float*)(vt + 2 * BF_DH * VTS);  // [128] pooling
+  lds_short* const x = XTile::ptr();
 
-  BF_STAMP();  // 0: kernel start
-  // ---- embed: x[s][c] = tok_emb[byte+3 or 0][c] + pos_emb[s][c] ----
-  {
-    const int s0 = start[line], e0 = end[line];
-    for (int i = tid * 8; i < BF_S * BF_H; i += BF_THREADS * 8) {
-      const int s = i / BF_H, c = i % BF_H;
-      int tok = 0;
-      const int idx = s0 + s;
-      if (idx < e0 && idx < max_len)
-        tok = (int)lines[(long)line * max_len + idx] + 3;
-      short8v te = *(const short8v*)(wb + WB_TOK + (long)tok * BF_H + c);
-      short8v pe = *(const short8v*)(wb + WB_POS + (long)s * BF_H + c);
-      short8v xv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        xv[j] = f32_to_bf16(bf16_to_f32(te[j]) + bf16_to_f32(pe[j]));
-      *(__attribute__((address_space(3))) short8v*)(x_lds + s * XS + c) = xv;
-    }
-  }
-  BF_STAMP();  // 1: embed work done
+  stamp.mark();
+  embed(lines, start, end, wb, x, line, max_len, tid);
+  stamp.mark();
   __syncthreads();
-  BF_STAMP();  // 2: embed barrier crossed
+  stamp.mark();
 
   for (int layer = 0; layer < n_layers; ++layer) {
     const short* lw = wb + WB_LAYER0 + (long)layer * LW_SIZE;
     const float* lf = fb + (long)layer * FB_SIZE;
 
-    // ---- qkv: Q|K -> buf[64][QKS], V -> vt transposed ----
     if (PHASES & PH_QKV)
-      block_gemm<BF_H, 3 * BF_H, 1, 0, BF_H, ABL>(x_lds, XS, (glob_cshort*)(lw + LW_QKV),
-                                             (glob_cfloat*)(lf + FB_BQKV), buf, QKS, x_lds, vt,
+      block_gemm<BF_H, 3 * BF_H, 1, 0, BF_H, ABL>(x, XS, (glob_cshort*)(lw + LW_QKV),
+                                             (glob_cfloat*)(lf + FB_BQKV), QkTile::ptr(), QKS, x, VtTile::ptr(),
                                              wid, lane);
-    BF_STAMP();  // qkv work done
+    stamp.mark();
     __syncthreads();
-    BF_STAMP();  // qkv barrier crossed
+    stamp.mark();
 
-    // ---- attention: wave = (head hh, 16 q-rows) ----
-    // Both MFMAs run operand-swapped (see block_gemm): S^T = K Q^T puts
-    // query q0 + (lane&15) and 16 keys (f*16 + (lane>>4)*4 + r) in each
-    // lane, so a softmax row is 15 in-lane ops plus two cross-lane steps
-    // (xor 16, 32) instead of four, every lane of a query ends up holding
-    // that query's 1/sum, and P leaves as four 8-byte stores. O^T = V^T P^T
-    // again gives the lane its own query and four consecutive d: scaled by
-    // the in-lane 1/sum (no __shfl) and stored 8 bytes at a time.
-    if (PHASES & PH_ATTN) {
-      const int hh = wid >> 2;
-      const int q0 = (wid & 3) * 16;
-      const int l15 = lane & 15;
-      const int l4 = lane >> 4;
-      const float scale = 0.125f;  // 1/sqrt(64)
-
-      f32x4 acc_p[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) acc_p[f] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < BF_DH / 32; ++ks) {
-        bf16x8 qf = *(const __attribute__((address_space(3))) bf16x8*)(
-            buf + (q0 + l15) * QKS + hh * BF_DH + ks * 32 + l4 * 8);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          bf16x8 kf = *(const __attribute__((address_space(3))) bf16x8*)(
-              buf + (f * 16 + l15) * QKS + BF_H + hh * BF_DH + ks * 32 +
-              l4 * 8);
-          acc_p[f] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, acc_p[f], 0, 0, 0);
-        }
-      }
-      float m = -1e30f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m = fmaxf(m, acc_p[f][r] * scale);
-      m = fmaxf(m, __shfl_xor(m, 16, 64));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-      float sum = 0.f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = __expf(acc_p[f][r] * scale - m);
-          acc_p[f][r] = e;
-          sum += e;
-        }
-      sum += __shfl_xor(sum, 16, 64);
-      sum += __shfl_xor(sum, 32, 64);
-      const float inv = 1.f / sum;
-      // P tiles alias the Q|K area: every wave must be done reading Q/K
-      __syncthreads();
-      lds_short* my_p = buf + wid * 16 * VTS;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-        *(lds_short4*)(my_p + l15 * VTS + f * 16 + l4 * 4) =
-            pack_bf16x4(acc_p[f]);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-local P
-
-      f32x4 acc_o[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) acc_o[f] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < BF_S / 32; ++ks) {
-        bf16x8 pf = *(const __attribute__((address_space(3))) bf16x8*)(
-            my_p + l15 * VTS + ks * 32 + l4 * 8);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          bf16x8 vf = *(const __attribute__((address_space(3))) bf16x8*)(
-              vt + (hh * BF_DH + f * 16 + l15) * VTS + ks * 32 + l4 * 8);
-          acc_o[f] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc_o[f], 0, 0, 0);
-        }
-      }
-      // attn out -> buf[O_OFF + q*XS + hh*64 + d] (disjoint from P tiles)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        f32x4 o = acc_o[f];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] *= inv;
-        *(lds_short4*)(buf + O_OFF + (q0 + l15) * XS + hh * BF_DH + f * 16 +
-                       l4 * 4) = pack_bf16x4(o);
-      }
-    }
-    BF_STAMP();  // attention work done
+    if (PHASES & PH_ATTN) attention(wid, lane);
+    stamp.mark();
     __syncthreads();
-    BF_STAMP();  // attention barrier crossed
+    stamp.mark();
 
-    // ---- proj: x += Wo(attn) ; LN1 ----
+    // x += Wo(attn); LN1
     if (PHASES & PH_PROJ)
-      block_gemm<BF_H, BF_H, 2, 0, BF_H, ABL>(buf + O_OFF, XS, (glob_cshort*)(lw + LW_WO),
-                                         (glob_cfloat*)(lf + FB_BO), nullptr, 0, x_lds,
+      block_gemm<BF_H, BF_H, 2, 0, BF_H, ABL>(AttnOut::ptr(), XS, (glob_cshort*)(lw + LW_WO),
+                                         (glob_cfloat*)(lf + FB_BO), nullptr, 0, x,
                                          nullptr, wid, lane);
     __syncthreads();
     if (PHASES & PH_LN)
-      block_layernorm(x_lds, lw + LW_LN1G, lw + LW_LN1B, wid, lane, eps);
-    BF_STAMP();  // proj+LN1 work done
+      block_layernorm(x, lw + LW_LN1G, lw + LW_LN1B, wid, lane, eps);
+    stamp.mark();
     __syncthreads();
-    BF_STAMP();  // proj+LN1 barrier crossed
+    stamp.mark();
 
-    // ---- FFN in two K=256 halves: buf = gelu(x@W1_h); x += buf@W2_h ----
+    // FFN in two K=256 halves: buf = gelu(x @ W1_h); x += buf @ W2_h; LN2
     if (PHASES & PH_FFN)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       block_gemm<BF_H, BF_FFN / 2, 0, 1, BF_H, ABL>(
-          x_lds, XS, (glob_cshort*)(lw + LW_W1 + (long)h * (BF_FFN / 2) * BF_H),
-          (glob_cfloat*)(lf + FB_B1 + h * (BF_FFN / 2)), buf, QKS, nullptr,
+          x, XS, (glob_cshort*)(lw + LW_W1 + (long)h * (BF_FFN / 2) * BF_H),
+          (glob_cfloat*)(lf + FB_B1 + h * (BF_FFN / 2)), FfnHalf::ptr(), QKS, nullptr,
           nullptr, wid, lane);
       __syncthreads();
       // bias b2 added once (half 0); half 1 adds only the partial product
@@ -528,49 +591,25 @@ static __device__ __forceinline__ void bert_fused_body(
       // noinline callee, put an exec-mask branch in front of every quad)
       if (h == 0)
         block_gemm<BF_FFN / 2, BF_H, 2, 0, BF_FFN, ABL, true>(
-            buf, QKS, (glob_cshort*)(lw + LW_W2), (glob_cfloat*)(lf + FB_B2),
-            nullptr, 0, x_lds, nullptr, wid, lane);
+            FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2), (glob_cfloat*)(lf + FB_B2),
+            nullptr, 0, x, nullptr, wid, lane);
       else
         block_gemm<BF_FFN / 2, BF_H, 2, 0, BF_FFN, ABL, false>(
-            buf, QKS, (glob_cshort*)(lw + LW_W2 + (long)h * (BF_FFN / 2)),
-            nullptr, nullptr, 0, x_lds, nullptr, wid, lane);
+            FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2 + (long)h * (BF_FFN / 2)),
+            nullptr, nullptr, 0, x, nullptr, wid, lane);
       __syncthreads();
     }
     if (PHASES & PH_LN)
-      block_layernorm(x_lds, lw + LW_LN2G, lw + LW_LN2B, wid, lane, eps);
-    BF_STAMP();  // ffn+LN2 work done
+      block_layernorm(x, lw + LW_LN2G, lw + LW_LN2B, wid, lane, eps);
+    stamp.mark();
     __syncthreads();
-    BF_STAMP();  // ffn+LN2 barrier crossed
+    stamp.mark();
   }
 
-  // ---- pool (mean over S) + score head ----
-  {
-    if (tid < BF_H) {
-      float s = 0.f;
-      for (int row = 0; row < BF_S; ++row)
-        s += bf16_to_f32(x_lds[row * XS + tid]);
-      const float w =
-          bf16_to_f32(wb[WB_LAYER0 + (long)n_layers * LW_SIZE + tid]);
-      red[tid] = (s / BF_S) * w;
-    }
-    __syncthreads();
-    if (wid == 0) {
-      float v = red[lane] + red[lane + 64];
-      v = warp_reduce_sum_f32(v);
-      if (lane == 0)
-        scores[line] = v + fb[(long)n_layers * FB_SIZE];  // b_score
-    }
-  }
-  BF_STAMP();  // final
-  if constexpr (TIMED) {
-    if (lane == 0 && stamps_out != nullptr) {
-      unsigned long long* dst =
-          stamps_out + ((long)line * BF_WAVES + wid) * BF_NSTAMP;
-      for (int k = 0; k < BF_NSTAMP; ++k)
-        dst[k] = k < tidx ? tstamp[k] : 0ull;
-    }
-  }
-#undef BF_STAMP
+  pool_score(wb + WB_LAYER0 + (long)n_layers * LW_SIZE,
+             fb + (long)n_layers * FB_SIZE, scores + line, tid);
+  stamp.mark();
+  stamp.flush(stamps_out, line, wid, lane);
 }
 
 extern "C" __global__ __launch_bounds__(BF_THREADS, 4)
@@ -585,8 +624,8 @@ void dmx_bert_fused_bf16(const unsigned char* __restrict__ lines,
                           n_layers, eps);
 }
 
-// probe variants (in-kernel phase ablation; guide §5.4 rule 19: co-compiled
-// variants can perturb codegen by a few % — read the deltas, not absolutes)
+// probe variants (in-kernel phase ablation; co-compiled variants can
+// perturb codegen by a few % — read the deltas, not absolutes)
 template <int PHASES, int ABL = 0>
 __global__ __launch_bounds__(BF_THREADS, 4) void dmx_bert_fused_probe(
     const unsigned char* lines, const int* start, const int* end,
@@ -612,10 +651,11 @@ void dmx_bert_fused_timed(const unsigned char* lines, const int* start,
 // keeps the attribute call off the production kernel's per-launch path
 // (unsynchronised on purpose: a racing second call sets the same value).
 constexpr int BF_MAX_DEVICES = 64;
+typedef bool AttrDone[BF_MAX_DEVICES];
 
 template <typename... KArgs, typename... Args>
 static hipError_t launch_bert_fused(void (*kernel)(KArgs...),
-                                    bool (&attr_done)[BF_MAX_DEVICES], int B,
+                                    AttrDone& attr_done, int B,
                                     hipStream_t stream, Args... args) {
   int dev = 0;
   hipError_t err = hipGetDevice(&dev);
@@ -637,7 +677,7 @@ extern "C" hipError_t dmx_launch_bert_fused_bf16(
     const uint8_t* lines, const int32_t* start, const int32_t* end,
     const int16_t* wb, const float* fb, float* scores, int B, int max_len,
     int n_layers, float eps, hipStream_t stream) {
-  static bool attr_done[BF_MAX_DEVICES];
+  static AttrDone attr_done;
   return launch_bert_fused(dmx_bert_fused_bf16, attr_done, B, stream, lines,
                            start, end, wb, fb, scores, B, max_len, n_layers,
                            eps);
@@ -647,56 +687,56 @@ extern "C" hipError_t dmx_launch_bert_fused_timed(
     const uint8_t* lines, const int32_t* start, const int32_t* end,
     const int16_t* wb, const float* fb, float* scores, int64_t* stamps, int B,
     int max_len, int n_layers, float eps, hipStream_t stream) {
-  static bool attr_done[BF_MAX_DEVICES];
+  static AttrDone attr_done;
   return launch_bert_fused(dmx_bert_fused_timed, attr_done, B, stream, lines,
                            start, end, wb, fb, scores, B, max_len, n_layers,
                            eps, (unsigned long long*)stamps);
 }
 
-// Compiled probe variants as X(phases, ablation); phase_mask = PH | AB << 8.
-#define BF_PROBE_VARIANTS(X)                                                 \
-  X(0, 0)                                                                    \
-  X(PH_QKV, 0)                                                               \
-  X(PH_QKV | PH_ATTN, 0)                                                     \
-  X(PH_QKV | PH_ATTN | PH_PROJ, 0)                                           \
-  X(PH_QKV | PH_ATTN | PH_PROJ | PH_LN, 0)                                   \
-  X(PH_ALL, 0)                                                               \
-  X(PH_FFN, 0)                                                               \
-  X(PH_LN, 0)                                                                \
-  /* perf-ablation variants (numerically wrong by design): */                \
-  X(PH_ALL, 1) /* B operand constant (no L2 weight loads) */                 \
-  X(PH_ALL, 2) /* A operand constant (no LDS activation reads) */            \
-  X(PH_ALL, 3) /* both constant (pure MFMA + epilogue) */                    \
-  X(PH_FFN, 1)                                                               \
-  X(PH_FFN, 2)                                                               \
-  X(PH_FFN, 3)
+// The compiled probe variants; phase_mask = phases | ablation << 8.
+struct ProbeVariant {
+  int mask;
+  decltype(&dmx_bert_fused_probe<0, 0>) kernel;
+  AttrDone attr_done;
+};
+template <int PHASES, int ABL = 0>
+constexpr ProbeVariant probe_variant() {
+  return {PHASES | (ABL << 8), dmx_bert_fused_probe<PHASES, ABL>, {}};
+}
+static ProbeVariant probe_variants[] = {
+    probe_variant<0>(),
+    probe_variant<PH_QKV>(),
+    probe_variant<PH_QKV | PH_ATTN>(),
+    probe_variant<PH_QKV | PH_ATTN | PH_PROJ>(),
+    probe_variant<PH_QKV | PH_ATTN | PH_PROJ | PH_LN>(),
+    probe_variant<PH_ALL>(),
+    probe_variant<PH_FFN>(),
+    probe_variant<PH_LN>(),
+    // perf-ablation variants (numerically wrong by design):
+    probe_variant<PH_ALL, 1>(),  // B operand constant (no L2 weight loads)
+    probe_variant<PH_ALL, 2>(),  // A operand constant (no LDS reads)
+    probe_variant<PH_ALL, 3>(),  // both constant (pure MFMA + epilogue)
+    probe_variant<PH_FFN, 1>(),
+    probe_variant<PH_FFN, 2>(),
+    probe_variant<PH_FFN, 3>(),
+};
+
+static ProbeVariant* find_probe_variant(int phase_mask) {
+  for (ProbeVariant& v : probe_variants)
+    if (v.mask == phase_mask) return &v;
+  return nullptr;
+}
 
 extern "C" bool dmx_bert_fused_probe_mask_known(int phase_mask) {
-  switch (phase_mask) {
-#define KNOWN(PH, AB) case ((PH) | ((AB) << 8)):
-    BF_PROBE_VARIANTS(KNOWN)
-#undef KNOWN
-    return true;
-    default:
-      return false;
-  }
+  return find_probe_variant(phase_mask) != nullptr;
 }
 
 extern "C" hipError_t dmx_launch_bert_fused_probe(
     const uint8_t* lines, const int32_t* start, const int32_t* end,
     const int16_t* wb, const float* fb, float* scores, int B, int max_len,
     int n_layers, float eps, int phase_mask, hipStream_t stream) {
-  switch (phase_mask) {
-#define LAUNCH_PROBE(PH, AB)                                                 \
-  case ((PH) | ((AB) << 8)): {                                               \
-    static bool attr_done[BF_MAX_DEVICES];                                   \
-    return launch_bert_fused(dmx_bert_fused_probe<PH, AB>, attr_done, B,     \
-                             stream, lines, start, end, wb, fb, scores, B,   \
-                             max_len, n_layers, eps);                        \
-  }
-    BF_PROBE_VARIANTS(LAUNCH_PROBE)
-#undef LAUNCH_PROBE
-    default:
-      return hipErrorInvalidValue;
-  }
+  ProbeVariant* v = find_probe_variant(phase_mask);
+  if (v == nullptr) return hipErrorInvalidValue;
+  return launch_bert_fused(v->kernel, v->attr_done, B, stream, lines, start,
+                           end, wb, fb, scores, B, max_len, n_layers, eps);
 }

@@ -234,11 +234,26 @@ def test_probe_and_timed_entry_points(model_pairs):
     st = stamps.cpu()
     assert st.shape[0] == 4 and (st[..., 19] >= st[..., 0]).all()
     assert (st[..., 0] > 0).all()
-    # phase subsets run; operand ablations (numerically wrong by design)
-    # still finish with finite scores
-    for phases in (0, 1, 3, 7, 15, 16, 8):
+    # stamp slots: 2 layers record 3 + 2 * 8 + 1 = 20 stamps per wave, in
+    # time order; the two unused slots are flushed as zero
+    used = st[..., :20]
+    assert (used[..., 1:] >= used[..., :-1]).all(), "stamp slots out of order"
+    assert (st[..., 20:] == 0).all(), "unused stamp slots are not zero"
+    # probe mask -> variant: every phase subset runs, and each mask reaches
+    # its own kernel
+    probe = {}
+    for phases in (0, 1, 3, 7, 15, 16, 8, 31):
         out = _dmx_C.bert_fused_probe(lines, start, end, wb, fb, 2, 1e-5, phases)
         assert out.shape == (4,)
+        probe[phases] = out
+    # qkv and attention write only buf and vt, never x
+    assert torch.equal(probe[1], probe[0]) and torch.equal(probe[3], probe[0])
+    distinct = (0, 7, 15, 31, 16, 8)
+    for i, a in enumerate(distinct):
+        for b in distinct[i + 1:]:
+            assert not torch.equal(probe[a], probe[b]), (a, b)
+    # operand ablations (numerically wrong by design) still finish with
+    # finite scores
     for phases in (31, 16):
         for abl in (1, 2, 3):
             out = _dmx_C.bert_fused_probe(lines, start, end, wb, fb, 2, 1e-5,
