@@ -10,6 +10,16 @@ normalized distance
     d(x) = sqrt(mean_i ((x_i - mu_i)^2 / (var_i + eps)))
 
 exceeds ``z_threshold``. Fully checkpointable (weights + moments).
+
+``embed_path`` picks how a batch is embedded. ``"layered"`` (default) runs
+the per-op transformer body and does the moments and the distance on the
+host. ``"fused"`` keeps everything on the device: training batches go
+through ``BertTinyDetectorModel.embed_spans`` into device-resident
+``EmbeddingStats``, a detect batch is one ``embed_distance_spans`` call (on
+a GPU with the flagship geometry, one launch of the fused kernel's distance
+head), the threshold compare runs there too, and only the alerting rows and
+their distances are read back. Where the fused kernel does not apply the
+model falls back to its layered body; the path never raises for that.
 """
 from __future__ import annotations
 
@@ -19,7 +29,12 @@ from typing import Any, Dict, List, Optional
 import torch
 
 from ...components.base import CoreDetector, CoreDetectorConfig
-from ...models.bert_tiny import BertTinyConfig, BertTinyDetectorModel
+from ...models.bert_tiny import (
+    BertTinyConfig,
+    BertTinyDetectorModel,
+    EmbeddingStats,
+    embedding_distance,
+)
 from ...schemas import DetectorSchema, ParserSchema
 from ... import ops
 
@@ -35,6 +50,9 @@ class EmbeddingDetectorConfig(CoreDetectorConfig):
     device: Optional[str] = None
     seed: int = 1234
     batch_max_len: int = 256
+    #: "layered": per-op body, host moments and distance. "fused": device
+    #: end to end through the fused kernel's embedding / distance head.
+    embed_path: str = "layered"
 
 
 class EmbeddingDetector(CoreDetector):
@@ -52,51 +70,73 @@ class EmbeddingDetector(CoreDetector):
             device=self.device, seed=cfg.seed,
         )
         self.detector_id = f"embedding_detector-{id(self):x}"
-        h = cfg.hidden
-        self._sum = torch.zeros(h, dtype=torch.float64)
-        self._sumsq = torch.zeros(h, dtype=torch.float64)
-        self._n = 0
+        if cfg.embed_path not in ("layered", "fused"):
+            raise ValueError(
+                f"embed_path must be 'layered' or 'fused', got {cfg.embed_path!r}")
+        self._fused = cfg.embed_path == "fused"
+        # the layered path keeps its moments on the host, where it embeds to
+        self.stats = EmbeddingStats(
+            cfg.hidden, device=self.device if self._fused else "cpu")
+
+    # the moments, under the names they had before EmbeddingStats held them
+    @property
+    def _sum(self) -> torch.Tensor:
+        return self.stats.sum
+
+    @property
+    def _sumsq(self) -> torch.Tensor:
+        return self.stats.sumsq
+
+    @property
+    def _n(self) -> int:
+        return self.stats.n
 
     # ------------------------------------------------------------------
-    def embed(self, raw_lines: List[bytes]) -> torch.Tensor:
-        """Mean-pooled transformer embeddings [B, hidden] (f32)."""
+    def _pack(self, raw_lines: List[bytes]):
+        """(lines, start, end) on the device: the whole line is the span."""
         lines, lens = ops.pack_lines(
             raw_lines, self.config.batch_max_len, device=self.device
         )
         start = torch.zeros(len(raw_lines), dtype=torch.int32, device=self.device)
-        tokens = self.model.tokenize_spans(lines, start, lens.int())
-        c = self.model.config
-        x = self.model.tok_emb[tokens.long()] + self.model.pos_emb[: c.max_seq].unsqueeze(0)
-        # full forward reusing the layered/fused ops, capturing pooled state
-        scores_unused = None
-        # run the transformer body (same math as forward, minus score head)
-        x = x.to(self.model.dtype).contiguous()
-        B, S = tokens.shape
-        M = B * S
-        h = c.hidden
-        for layer in self.model.layers:
-            x2 = x.view(M, h)
-            qkv = ops.fused_linear(x2, layer["wqkv_t"], layer["bqkv"])
-            attn = ops.attention_qkv(qkv.view(B, S, 3 * h), S, c.heads, c.head_dim).view(M, h)
-            proj = ops.fused_linear(attn, layer["wo_t"], layer["bo"])
-            x1 = ops.layernorm(proj, layer["ln1_g"], layer["ln1_b"], residual=x2)
-            ffn = ops.fused_linear(x1, layer["w1_t"], layer["b1"], activation="gelu")
-            ffn = ops.fused_linear(ffn, layer["w2_t"], layer["b2"])
-            x = ops.layernorm(ffn, layer["ln2_g"], layer["ln2_b"], residual=x1).view(B, S, h)
-        return x.float().mean(dim=1).cpu()
+        return lines, start, lens.int()
+
+    def embed(self, raw_lines: List[bytes]) -> torch.Tensor:
+        """Mean-pooled transformer embeddings [B, hidden] (f32), on the host.
+        Always the layered body, whatever ``embed_path`` says."""
+        lines, start, end = self._pack(raw_lines)
+        tokens = self.model.tokenize_spans(lines, start, end)
+        return self.model._encode(tokens).float().mean(dim=1).cpu()
 
     def train(self, parsed_batch: List[ParserSchema]) -> None:
-        emb = self.embed([(p.log or "").encode() for p in parsed_batch])
-        self._sum += emb.double().sum(dim=0)
-        self._sumsq += (emb.double() ** 2).sum(dim=0)
-        self._n += emb.shape[0]
+        raw = [(p.log or "").encode() for p in parsed_batch]
+        if self._fused:
+            self.stats.update(self.model.embed_spans(*self._pack(raw)))
+        else:
+            self.stats.update(self.embed(raw))
 
     def _distance(self, emb: torch.Tensor) -> torch.Tensor:
+        if self._fused:
+            return embedding_distance(
+                emb.to(self.stats.device), self.stats.mu, self.stats.inv_var)
         n = max(self._n, 1)
         mu = (self._sum / n).float()
         var = (self._sumsq / n).float() - mu ** 2
         z2 = (emb - mu) ** 2 / (var.clamp(min=1e-6))
         return z2.mean(dim=1).sqrt()
+
+    def _alerting(self, raw_lines: List[bytes]) -> List[tuple]:
+        """[(row, distance)] of the lines beyond the threshold."""
+        thr = float(self.config.z_threshold)
+        if not self._fused:
+            dist = self._distance(self.embed(raw_lines))
+            return [(j, d) for j, d in enumerate(dist.tolist()) if not d <= thr]
+        dist = self.model.embed_distance_spans(
+            *self._pack(raw_lines), self.stats.mu, self.stats.inv_var)
+        rows = torch.nonzero(dist > thr).flatten()
+        # one readback: row numbers and distances, both exact in f64
+        both = torch.cat([rows.double(), dist[rows].double()]).cpu()
+        k = rows.numel()
+        return list(zip((int(r) for r in both[:k].tolist()), both[k:].tolist()))
 
     def process_batch(self, frames: List[bytes]) -> List[Optional[bytes]]:
         parsed = [ParserSchema.deserialize(f) for f in frames]
@@ -110,13 +150,10 @@ class EmbeddingDetector(CoreDetector):
         rest = parsed[train_upto:]
         if not rest or self._n == 0:
             return results
-        emb = self.embed([(p.log or "").encode() for p in rest])
-        dist = self._distance(emb)
         now = int(time.time())
         thr = float(self.config.z_threshold)
-        for j, (p, d) in enumerate(zip(rest, dist.tolist())):
-            if d <= thr:
-                continue
+        for j, d in self._alerting([(p.log or "").encode() for p in rest]):
+            p = rest[j]
             results[train_upto + j] = DetectorSchema(
                 detectorID=self.detector_id,
                 detectorType="embedding_detector",
@@ -140,13 +177,11 @@ class EmbeddingDetector(CoreDetector):
     def state_dict(self) -> Dict[str, Any]:
         return {
             "seen_lines": self._seen_lines,
-            "sum": self._sum, "sumsq": self._sumsq, "n": self._n,
+            **self.stats.state_dict(),  # sum, sumsq (CPU f64), n
             "model": self.model.state_dict(),
         }
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
         self._seen_lines = int(state.get("seen_lines", 0))
-        self._sum = state["sum"]
-        self._sumsq = state["sumsq"]
-        self._n = int(state["n"])
+        self.stats.load_state_dict(state)
         self.model.load_state_dict(state["model"])

@@ -35,6 +35,9 @@ class FusedPipelineDetectorConfig(CoreConfig):
     hashset_capacity: int = 1 << 16
     use_transformer: bool = True
     score_threshold: float = 3.0
+    #: "head": the model's score head. "embedding": distance from the
+    #: Gaussian fitted to the embeddings of the data_use_training rows.
+    score_mode: str = "head"
     data_use_training: int = 0
     device: Optional[str] = None
     seed: int = 1234
@@ -71,6 +74,7 @@ class FusedPipelineDetector(CoreComponent):
                 hashset_capacity=cfg.hashset_capacity,
                 use_transformer=cfg.use_transformer,
                 score_threshold=cfg.score_threshold,
+                score_mode=cfg.score_mode,
                 train_lines=cfg.data_use_training,
                 seed=cfg.seed,
             ),
@@ -170,7 +174,9 @@ class FusedPipelineDetector(CoreComponent):
                 reasons.append("unknown watched value")
             if (self.pipe.model is not None
                     and float(scores[i]) > self.config.score_threshold):
-                reasons.append(f"score {float(scores[i]):.3f}")
+                what = ("embedding distance"
+                        if self.pipe.embedding_stats is not None else "score")
+                reasons.append(f"{what} {float(scores[i]):.3f}")
             lid = id_of(i)
             alerts.append((i, DetectorSchema(
                 detectorID=self.detector_id,
@@ -311,6 +317,8 @@ class FusedPipelineDetector(CoreComponent):
             state["hashsets"] = self.pipe.hashsets.state_dict()
         if self.pipe.model is not None:
             state["model"] = self.pipe.model.state_dict()
+        if self.pipe.embedding_stats is not None:
+            state["embedding_stats"] = self.pipe.embedding_stats.state_dict()
         return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
@@ -319,3 +327,5 @@ class FusedPipelineDetector(CoreComponent):
             self.pipe.hashsets.load_state_dict(state["hashsets"])
         if "model" in state and self.pipe.model is not None:
             self.pipe.model.load_state_dict(state["model"])
+        if "embedding_stats" in state and self.pipe.embedding_stats is not None:
+            self.pipe.embedding_stats.load_state_dict(state["embedding_stats"])

@@ -48,6 +48,77 @@ def _fused_layout(n_layers: int) -> dict:
     return _dmx_C.bert_fused_layout(n_layers)
 
 
+def embedding_distance(
+    emb: torch.Tensor, mu: torch.Tensor, inv_var: torch.Tensor
+) -> torch.Tensor:
+    """sqrt(mean_i((x_i - mu_i)^2 * inv_var_i)) per row, in torch."""
+    return ((emb - mu) ** 2 * inv_var).mean(dim=1).sqrt()
+
+
+class EmbeddingStats:
+    """Running first and second moments of embeddings: the diagonal Gaussian
+    the embedding detectors measure distance from.
+
+    ``sum`` and ``sumsq`` (f64) and ``n`` live on the model's device and are
+    accumulated there with torch (training is not the hot path). ``mu`` and
+    ``inv_var = 1 / clamp(sumsq/n - mu^2, min=VAR_FLOOR)`` are f32 device
+    tensors, recomputed after an ``update`` or a restore into the SAME two
+    buffers, so a captured graph that reads them keeps reading the current
+    values. The checkpoint carries the moments as CPU f64 under the keys
+    ``sum``, ``sumsq`` and ``n``.
+    """
+
+    VAR_FLOOR = 1e-6
+
+    def __init__(self, hidden: int, device: str | torch.device = "cpu") -> None:
+        self.device = torch.device(device)
+        self.sum = torch.zeros(hidden, dtype=torch.float64, device=self.device)
+        self.sumsq = torch.zeros(hidden, dtype=torch.float64, device=self.device)
+        self.n = 0
+        self._mu = torch.zeros(hidden, dtype=torch.float32, device=self.device)
+        self._inv_var = torch.zeros_like(self._mu)
+        self._stale = True
+
+    def update(self, emb: torch.Tensor) -> None:
+        """Accumulate embeddings [B, hidden] (any float dtype, any device)."""
+        if emb.shape[0] == 0:
+            return
+        e = emb.to(self.device).double()
+        self.sum += e.sum(dim=0)
+        self.sumsq += (e * e).sum(dim=0)
+        self.n += int(emb.shape[0])
+        self._stale = True
+
+    def _refresh(self) -> None:
+        n = max(self.n, 1)
+        mu = self.sum / n
+        var = (self.sumsq / n - mu * mu).clamp(min=self.VAR_FLOOR)
+        self._mu.copy_(mu)            # the only f32 step: the final cast
+        self._inv_var.copy_(1.0 / var)
+        self._stale = False
+
+    @property
+    def mu(self) -> torch.Tensor:
+        if self._stale:
+            self._refresh()
+        return self._mu
+
+    @property
+    def inv_var(self) -> torch.Tensor:
+        if self._stale:
+            self._refresh()
+        return self._inv_var
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"sum": self.sum.cpu(), "sumsq": self.sumsq.cpu(), "n": self.n}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.sum = state["sum"].to(self.device, torch.float64)
+        self.sumsq = state["sumsq"].to(self.device, torch.float64)
+        self.n = int(state["n"])
+        self._stale = True
+
+
 class BertTinyDetectorModel:
     """Inference-first model over custom ops (no autograd graph needed for
     the streaming detector; training/calibration uses score statistics)."""
@@ -92,8 +163,10 @@ class BertTinyDetectorModel:
         self.b_score = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------
-    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
-        """tokens [B, S] int64/int32 -> anomaly scores [B] (f32)."""
+    def _encode(self, tokens: torch.Tensor) -> torch.Tensor:
+        """tokens [B, S] -> final hidden states [B, S, hidden] (model dtype):
+        the layered transformer body that ``forward`` and the embedding
+        fallback share."""
         c = self.config
         B, S = tokens.shape
         assert S <= c.max_seq
@@ -118,8 +191,11 @@ class BertTinyDetectorModel:
             ffn = ops.fused_linear(ffn, layer["w2_t"], layer["b2"])
             x = ops.layernorm(ffn, layer["ln2_g"], layer["ln2_b"], residual=x1)
             x = x.view(B, S, h)
+        return x
 
-        pooled = x.float().mean(dim=1)  # [B, h]
+    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
+        """tokens [B, S] int64/int32 -> anomaly scores [B] (f32)."""
+        pooled = self._encode(tokens).float().mean(dim=1)  # [B, h]
         scores = pooled @ self.w_score.float() + self.b_score
         return scores.squeeze(-1)
 
@@ -212,6 +288,55 @@ class BertTinyDetectorModel:
             )
         tokens = self.tokenize_spans(lines, start.int(), end.int())
         return self.forward(tokens)
+
+    def _fused_embed(self, lines, start, end, mu, inv_var, want_emb):
+        from ..ops import _dmx_C  # type: ignore[attr-defined]
+
+        wb, fb = self._fused_blobs()
+        return _dmx_C.bert_fused_embed(
+            lines, start.int().contiguous(), end.int().contiguous(),
+            wb, fb, self.config.layers, 1e-5, mu, inv_var, want_emb,
+        )
+
+    def embed_spans(
+        self, lines: torch.Tensor, start: torch.Tensor, end: torch.Tensor
+    ) -> torch.Tensor:
+        """lines [B, max_len] u8 + content spans -> mean-pooled final hidden
+        states [B, hidden] f32. Dispatches like ``score_spans``: the fused
+        kernel with its embedding head, or tokenize + the layered body."""
+        if lines.shape[0] == 0:
+            return torch.zeros((0, self.config.hidden), dtype=torch.float32,
+                               device=lines.device)
+        if self._fused_ok():
+            return self._fused_embed(lines, start, end, None, None, True)[0]
+        tokens = self.tokenize_spans(lines, start.int(), end.int())
+        return self._encode(tokens).float().mean(dim=1)
+
+    def embed_distance_spans(
+        self,
+        lines: torch.Tensor,
+        start: torch.Tensor,
+        end: torch.Tensor,
+        mu: torch.Tensor,        # [hidden] f32
+        inv_var: torch.Tensor,   # [hidden] f32
+        return_emb: bool = False,
+    ):
+        """Normalised distance of each line's embedding from a fitted
+        diagonal Gaussian, ``sqrt(mean_i((x_i - mu_i)^2 * inv_var_i))``
+        [B] f32; with ``return_emb`` the pair (distance, embedding). On the
+        fused path the distance is computed in the kernel and, without
+        ``return_emb``, the embedding never leaves the chip."""
+        if lines.shape[0] == 0:
+            dist = torch.zeros(0, dtype=torch.float32, device=lines.device)
+            emb = torch.zeros((0, self.config.hidden), dtype=torch.float32,
+                              device=lines.device)
+        elif self._fused_ok():
+            emb, dist = self._fused_embed(lines, start, end, mu, inv_var,
+                                          return_emb)
+        else:
+            emb = self.embed_spans(lines, start, end)
+            dist = embedding_distance(emb, mu, inv_var)
+        return (dist, emb) if return_emb else dist
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         out = {"tok_emb": self.tok_emb, "pos_emb": self.pos_emb,

@@ -22,7 +22,9 @@
 // Schedule (bert_fused_body; every `|` is a block barrier):
 //   embed | per layer: qkv | attention (one barrier inside, before the P
 //   tiles overwrite Q|K) | x += Wo | LN1 | 2 x (W1 half + GELU | x += W2
-//   half |) LN2 | pool | score.
+//   half |) LN2 | pool | score. dmx_bert_fused_embed_bf16 runs the same
+//   schedule and ends in pool_embed instead: the pooled vector and / or its
+//   distance from a fitted diagonal Gaussian.
 //
 // Operand order. The 16x16x32 bf16 A and B fragment layouts are the same
 // function of the lane (row or column lane&15, k (lane>>4)*8..+7), so
@@ -484,6 +486,44 @@ static __device__ __forceinline__ void pool_score(
   }
 }
 
+// ---- pool (mean over S) + embedding / distance head ------------------------
+// The tail of dmx_bert_fused_embed_bf16: the pooled vector itself (emb, one
+// coalesced 512-byte row per block) and / or its normalised distance from a
+// fitted diagonal Gaussian, dist = sqrt(mean_c((m_c - mu_c)^2 * inv_var_c)).
+// emb and mu are kernel arguments, so both null tests are scalar branches;
+// inv_var and dist are read only when mu is given.
+static __device__ __forceinline__ void pool_embed(
+    float* __restrict__ emb, const float* __restrict__ mu,
+    const float* __restrict__ inv_var, float* __restrict__ dist, int line,
+    int tid) {
+  const lds_short* x_lds = XTile::ptr();
+  lds_float* red = (lds_float*)((lds_short*)smem_raw + RED_OFF);
+  if (tid < BF_H) {
+    float s = 0.f;
+    for (int row = 0; row < BF_S; ++row)
+      s += bf16_to_f32(x_lds[row * XS + tid]);
+    const float m = s / BF_S;
+    if (emb != nullptr) emb[(long)line * BF_H + tid] = m;
+    if (mu != nullptr) {
+      const float d = m - mu[tid];
+      red[tid] = d * d * inv_var[tid];
+    }
+  }
+  if (mu == nullptr) return;
+  __syncthreads();
+  const int wid = tid / DMX_WAVE, lane = tid % DMX_WAVE;
+  if (wid == 0) {
+    float v = red[lane] + red[lane + 64];
+    v = warp_reduce_sum_f32(v);
+    if (lane == 0) dist[line] = sqrtf(v / BF_H);
+  }
+}
+
+// The tail phase of bert_fused_body: the score head of the production, probe
+// and timed kernels, or the embedding / distance head.
+#define HEAD_SCORE 0
+#define HEAD_EMBED 1
+
 // Phase bits for the profiling probe (production uses PH_ALL; skipped
 // phases cannot be dead-code-eliminated backwards because every phase
 // ends in LDS stores).
@@ -522,8 +562,10 @@ struct StampRecorder<true> {
 
 // The schedule: phase, stamp, barrier, stamp. Stamp slots: 0 kernel start,
 // 1-2 embed, then per layer (work done, barrier crossed) for qkv,
-// attention, proj+LN1 and ffn+LN2, and one final stamp.
-template <int PHASES, bool TIMED = false, int ABL = 0>
+// attention, proj+LN1 and ffn+LN2, and one final stamp. HEAD picks the tail
+// phase; with HEAD_EMBED `scores` is unused, with HEAD_SCORE the four
+// arguments after `stamps_out` are.
+template <int PHASES, bool TIMED = false, int ABL = 0, int HEAD = HEAD_SCORE>
 static __device__ __forceinline__ void bert_fused_body(
     const unsigned char* __restrict__ lines,  // [B, max_len]
     const int* __restrict__ start,            // [B] content span start
@@ -532,7 +574,11 @@ static __device__ __forceinline__ void bert_fused_body(
     const float* __restrict__ fb,             // f32 bias blob
     float* __restrict__ scores,               // [B]
     int B, int max_len, int n_layers, float eps,
-    unsigned long long* __restrict__ stamps_out = nullptr) {
+    unsigned long long* __restrict__ stamps_out = nullptr,
+    float* __restrict__ emb = nullptr,            // [B, H] or null
+    const float* __restrict__ mu = nullptr,       // [H] or null
+    const float* __restrict__ inv_var = nullptr,  // [H], read when mu given
+    float* __restrict__ dist = nullptr) {         // [B], written when mu given
   StampRecorder<TIMED> stamp;
   const int line = blockIdx.x;
   if (line >= B) return;
@@ -606,8 +652,11 @@ static __device__ __forceinline__ void bert_fused_body(
     stamp.mark();
   }
 
-  pool_score(wb + WB_LAYER0 + (long)n_layers * LW_SIZE,
-             fb + (long)n_layers * FB_SIZE, scores + line, tid);
+  if constexpr (HEAD == HEAD_EMBED)
+    pool_embed(emb, mu, inv_var, dist, line, tid);
+  else
+    pool_score(wb + WB_LAYER0 + (long)n_layers * LW_SIZE,
+               fb + (long)n_layers * FB_SIZE, scores + line, tid);
   stamp.mark();
   stamp.flush(stamps_out, line, wid, lane);
 }
@@ -622,6 +671,26 @@ void dmx_bert_fused_bf16(const unsigned char* __restrict__ lines,
                          int n_layers, float eps) {
   bert_fused_body<PH_ALL>(lines, start, end, wb, fb, scores, B, max_len,
                           n_layers, eps);
+}
+
+// The same schedule with the embedding / distance head (pool_embed). A
+// separate __global__: the production kernel's instruction stream is the same
+// with and without it (profiles/r16_embed_head_isa.txt).
+extern "C" __global__ __launch_bounds__(BF_THREADS, 4)
+void dmx_bert_fused_embed_bf16(const unsigned char* __restrict__ lines,
+                               const int* __restrict__ start,
+                               const int* __restrict__ end,
+                               const short* __restrict__ wb,
+                               const float* __restrict__ fb,
+                               float* __restrict__ emb,
+                               const float* __restrict__ mu,
+                               const float* __restrict__ inv_var,
+                               float* __restrict__ dist, int B, int max_len,
+                               int n_layers, float eps) {
+  bert_fused_body<PH_ALL, false, 0, HEAD_EMBED>(lines, start, end, wb, fb,
+                                                nullptr, B, max_len, n_layers,
+                                                eps, nullptr, emb, mu, inv_var,
+                                                dist);
 }
 
 // probe variants (in-kernel phase ablation; co-compiled variants can
@@ -645,7 +714,7 @@ void dmx_bert_fused_timed(const unsigned char* lines, const int* start,
 }
 
 // ---- host side -------------------------------------------------------------
-// The one launch path of all three entry points. BF_LDS_BYTES is above the
+// The one launch path of all four entry points. BF_LDS_BYTES is above the
 // default dynamic-LDS limit, so each (kernel, device) pair needs the opt-in
 // attribute once; `attr_done` is that kernel's per-device flag array, which
 // keeps the attribute call off the production kernel's per-launch path
@@ -681,6 +750,17 @@ extern "C" hipError_t dmx_launch_bert_fused_bf16(
   return launch_bert_fused(dmx_bert_fused_bf16, attr_done, B, stream, lines,
                            start, end, wb, fb, scores, B, max_len, n_layers,
                            eps);
+}
+
+extern "C" hipError_t dmx_launch_bert_fused_embed(
+    const uint8_t* lines, const int32_t* start, const int32_t* end,
+    const int16_t* wb, const float* fb, float* emb, const float* mu,
+    const float* inv_var, float* dist, int B, int max_len, int n_layers,
+    float eps, hipStream_t stream) {
+  static AttrDone attr_done;
+  return launch_bert_fused(dmx_bert_fused_embed_bf16, attr_done, B, stream,
+                           lines, start, end, wb, fb, emb, mu, inv_var, dist,
+                           B, max_len, n_layers, eps);
 }
 
 extern "C" hipError_t dmx_launch_bert_fused_timed(

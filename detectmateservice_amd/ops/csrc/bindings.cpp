@@ -226,12 +226,22 @@ torch::Tensor attention_qkv_bf16(torch::Tensor qkv, int64_t S, int64_t H,
 
 // ---- fused BERT-tiny ------------------------------------------------------------
 
-// Everything the three fused entry points share, device clause last.
+// A [BF_H] f32 statistics vector of the embedding head (mu, inv_var).
+void check_embed_stat(const torch::Tensor& t, const char* name) {
+  check_arg(t, name, torch::kFloat32, 1);
+  check_numel(t, name, BF_H, "BF_H");
+}
+
+// Everything the fused entry points share, device clause last. The embed
+// entry point hands its two statistics vectors (both or neither) through
+// here so that their clauses also come before the device clause.
 DeviceScope check_bert_fused_args(const torch::Tensor& lines,
                                   const torch::Tensor& start,
                                   const torch::Tensor& end,
                                   const torch::Tensor& wb,
-                                  const torch::Tensor& fb, int64_t n_layers) {
+                                  const torch::Tensor& fb, int64_t n_layers,
+                                  const torch::Tensor* mu = nullptr,
+                                  const torch::Tensor* inv_var = nullptr) {
   check_arg(lines, "lines", torch::kUInt8, 2);
   const auto B = lines.size(0);
   check_arg(start, "start", torch::kInt32, 1);
@@ -250,8 +260,15 @@ DeviceScope check_bert_fused_args(const torch::Tensor& lines,
   TORCH_CHECK(reinterpret_cast<uintptr_t>(fb.data_ptr<float>()) % 16 == 0,
               "fb: bias blob must be 16-byte aligned, got storage offset ",
               fb.storage_offset(), " floats");
-  return DeviceScope(
-      {{"lines", lines}, {"start", start}, {"end", end}, {"wb", wb}, {"fb", fb}});
+  if (mu != nullptr) check_embed_stat(*mu, "mu");
+  if (inv_var != nullptr) check_embed_stat(*inv_var, "inv_var");
+  return DeviceScope({{"lines", lines},
+                      {"start", start},
+                      {"end", end},
+                      {"wb", wb},
+                      {"fb", fb},
+                      {"mu", mu != nullptr ? *mu : lines},
+                      {"inv_var", inv_var != nullptr ? *inv_var : lines}});
 }
 
 torch::Tensor bert_fused_bf16(torch::Tensor lines, torch::Tensor start,
@@ -269,6 +286,44 @@ torch::Tensor bert_fused_bf16(torch::Tensor lines, torch::Tensor start,
       (float)eps, dev.stream()));
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return scores;
+}
+
+// Same forward, embedding / distance head: (emb [B, BF_H] | None,
+// dist [B] | None). dist needs the fitted statistics mu and inv_var.
+py::tuple bert_fused_embed(torch::Tensor lines, torch::Tensor start,
+                           torch::Tensor end, torch::Tensor wb,
+                           torch::Tensor fb, int64_t n_layers, double eps,
+                           c10::optional<torch::Tensor> mu,
+                           c10::optional<torch::Tensor> inv_var,
+                           bool want_emb) {
+  const bool has_mu = mu.has_value() && mu->defined();
+  const bool has_iv = inv_var.has_value() && inv_var->defined();
+  TORCH_CHECK(!has_mu || has_iv, "inv_var must be given together with mu");
+  TORCH_CHECK(!has_iv || has_mu, "mu must be given together with inv_var");
+  TORCH_CHECK(want_emb || has_mu,
+              "want_emb must be true when mu and inv_var are not given: "
+              "there would be no output");
+  DeviceScope dev =
+      check_bert_fused_args(lines, start, end, wb, fb, n_layers,
+                            has_mu ? &*mu : nullptr, has_iv ? &*inv_var : nullptr);
+  const auto B = lines.size(0), max_len = lines.size(1);
+  const auto f32 = lines.options().dtype(torch::kFloat32);
+  torch::Tensor emb, dist;
+  if (want_emb) emb = torch::empty({B, BF_H}, f32);
+  if (has_mu) dist = torch::empty({B}, f32);
+  if (B > 0) {
+    C10_HIP_CHECK(dmx_launch_bert_fused_embed(
+        lines.data_ptr<uint8_t>(), start.data_ptr<int32_t>(),
+        end.data_ptr<int32_t>(), bf16_in(wb), fb.data_ptr<float>(),
+        want_emb ? emb.data_ptr<float>() : nullptr,
+        has_mu ? mu->data_ptr<float>() : nullptr,
+        has_mu ? inv_var->data_ptr<float>() : nullptr,
+        has_mu ? dist.data_ptr<float>() : nullptr, (int)B, (int)max_len,
+        (int)n_layers, (float)eps, dev.stream()));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+  return py::make_tuple(want_emb ? py::cast(emb) : py::none(),
+                        has_mu ? py::cast(dist) : py::none());
 }
 
 torch::Tensor bert_fused_probe(torch::Tensor lines, torch::Tensor start,
@@ -538,6 +593,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA MHA reading fused QKV layout [B,S,3*H*Dh] -> [B,S,H*Dh]");
   m.def("bert_fused_bf16", &bert_fused_bf16,
         "whole-model BERT-tiny forward, one workgroup per line");
+  m.def("bert_fused_embed", &bert_fused_embed,
+        "fused BERT-tiny forward with the embedding / distance head",
+        py::arg("lines"), py::arg("start"), py::arg("end"), py::arg("wb"),
+        py::arg("fb"), py::arg("n_layers"), py::arg("eps"),
+        py::arg("mu") = py::none(), py::arg("inv_var") = py::none(),
+        py::arg("want_emb") = true);
   m.def("bert_fused_probe", &bert_fused_probe,
         "phase-masked probe variant of the fused BERT kernel");
   m.def("bert_fused_timed", &bert_fused_timed,

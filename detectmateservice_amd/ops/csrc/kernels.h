@@ -118,6 +118,16 @@ hipError_t dmx_launch_bert_fused_bf16(const uint8_t* lines,
                                       float* scores, int B, int max_len,
                                       int n_layers, float eps,
                                       hipStream_t stream);
+// Same forward, embedding / distance head. emb [B, BF_H] or null; mu and
+// inv_var [BF_H], both or neither; dist [B], written when mu is given.
+hipError_t dmx_launch_bert_fused_embed(const uint8_t* lines,
+                                       const int32_t* start,
+                                       const int32_t* end, const int16_t* wb,
+                                       const float* fb, float* emb,
+                                       const float* mu, const float* inv_var,
+                                       float* dist, int B, int max_len,
+                                       int n_layers, float eps,
+                                       hipStream_t stream);
 // hipErrorInvalidValue when phase_mask names no compiled variant
 hipError_t dmx_launch_bert_fused_probe(const uint8_t* lines,
                                        const int32_t* start,
