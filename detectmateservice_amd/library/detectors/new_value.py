@@ -276,7 +276,18 @@ class NewValueComboDetector(CoreDetector):
         super().__init__(config)
         self.specs = _parse_specs(self.config)
         self.known_combos: Set[Tuple[Optional[str], ...]] = set()
+        #: combination hashes (docs/kernels.md, "Combination hash") of
+        #: `known_combos`, kept wherever that set is; the batched fast path
+        #: compares hashes and decodes only the rows it does not know
+        self.known_h: Set[int] = set()
         self.detector_id = f"new_value_combo_detector-{id(self):x}"
+        # the batched codec returns variable columns first, then headers
+        self._col_specs = (
+            [s for s in self.specs if s.kind == "variable"]
+            + [s for s in self.specs if s.kind == "header"]
+        )
+        #: column of each spec in the codec's output, in spec (= tuple) order
+        self._col_of = [self._col_specs.index(s) for s in self.specs]
 
     def _combo(self, parsed: ParserSchema) -> Tuple[Optional[str], ...]:
         return tuple(
@@ -285,9 +296,122 @@ class NewValueComboDetector(CoreDetector):
             if s.event_id is None or s.event_id == parsed.EventID
         )
 
+    def _relevance(self, event_id) -> Tuple[int, ...]:
+        return tuple(
+            1 if s.event_id is None or s.event_id == event_id else 0
+            for s in self.specs
+        )
+
+    def _learn_h(self, relevance: Tuple[int, ...], combo: Tuple[Optional[str], ...]) -> None:
+        """Hash one learnt tuple under one relevance pattern (which specs
+        produced its elements)."""
+        from ... import ops as _ops
+
+        if not combo:
+            return
+        values = iter(combo)
+        row = []
+        for r in relevance:
+            v = next(values) if r else None
+            row.append(0 if v is None else _ops.fnv1a64(v.encode("utf-8")))
+        import numpy as np
+
+        h = _ops.combo_fold([list(relevance)], np.array([row], dtype=np.uint64))
+        self.known_h.add(int(h[0]))
+
+    def _relevance_patterns(self) -> Set[Tuple[int, ...]]:
+        """Every relevance pattern a frame can have: one per configured
+        event id plus the one of any other event."""
+        events = {s.event_id for s in self.specs if s.event_id is not None}
+        return {self._relevance(e) for e in events} | {self._relevance(None)}
+
+    def _learn_combo(self, combo: Tuple[Optional[str], ...]) -> None:
+        """Learn a tuple whose event is not known (checkpoint, peer rank).
+        `known_combos` does not record which specs a tuple came from, so
+        detect() accepts it under every pattern of that length; known_h
+        does the same."""
+        self.known_combos.add(combo)
+        for pattern in self._relevance_patterns():
+            if sum(pattern) == len(combo):
+                self._learn_h(pattern, combo)
+
     def train(self, parsed_batch: List[ParserSchema]) -> None:
         for parsed in parsed_batch:
-            self.known_combos.add(self._combo(parsed))
+            combo = self._combo(parsed)
+            self.known_combos.add(combo)
+            self._learn_h(self._relevance(parsed.EventID), combo)
+
+    # ------------------------------------------------------------------
+    # batched service-path fast path, shaped like NewValueDetector's: one
+    # C++ decode+hash call for the member hashes, the combination hash
+    # folded on the host, full decode only for rows whose hash is unknown.
+    # ------------------------------------------------------------------
+    def process_batch(self, frames: List[bytes]) -> List[Optional[bytes]]:
+        from ... import ops as _ops
+
+        from ...components.base import BufferMode
+
+        mode = getattr(self.config, "buffer_mode", BufferMode.NO_BUF)
+        if isinstance(mode, str):
+            mode = BufferMode(mode)
+        if (
+            len(frames) < 8
+            or not _ops.have_extension()
+            or not self.specs
+            or mode != BufferMode.NO_BUF  # windowed modes need per-frame flow
+            # the C++ extractor applies header watches to every frame
+            or any(s.kind == "header" and s.event_id is not None for s in self.specs)
+        ):
+            return super().process_batch(frames)
+        try:
+            var_specs = [
+                (s.event_id if s.event_id is not None else -1, int(s.pos))
+                for s in self._col_specs if s.kind == "variable"
+            ]
+        except (TypeError, ValueError):  # extract() treats such a pos as absent
+            return super().process_batch(frames)
+        from ...ops import _dmx_C  # type: ignore[attr-defined]
+
+        hdr_names = [str(s.pos) for s in self._col_specs if s.kind == "header"]
+        hashes, event_ids, _log_ids = _dmx_C.parser_watch_hashes(
+            list(frames), var_specs, hdr_names, False
+        )
+        results: List[Optional[bytes]] = [None] * len(frames)
+
+        n_train = int(getattr(self.config, "data_use_training", 0))
+        train_upto = 0
+        if self._seen_lines < n_train:
+            train_upto = min(len(frames), n_train - self._seen_lines)
+            # training records the VALUES (state_dict format, python-path
+            # parity), so the training slice is decoded normally
+            self.train([ParserSchema.deserialize(f) for f in frames[:train_upto]])
+        self._seen_lines += len(frames)
+        if train_upto == len(frames):
+            return results
+
+        import numpy as np
+
+        ev = event_ids.numpy()[train_upto:]
+        member_h = hashes.numpy()[train_upto:][:, self._col_of]
+        relevant = np.stack(
+            [
+                np.ones(len(ev), dtype=np.uint8) if s.event_id is None
+                else (ev == s.event_id).astype(np.uint8)
+                for s in self.specs
+            ],
+            axis=1,
+        )
+        combo_h = _ops.combo_fold(relevant, member_h).tolist()
+        known_h = self.known_h
+        for k, h in enumerate(combo_h):
+            if h == 0 or h in known_h:
+                continue
+            # rare path: full decode + the per-frame alert semantics
+            parsed = ParserSchema.deserialize(frames[train_upto + k])
+            alert = DetectorSchema()
+            if self.detect(parsed, alert):
+                results[train_upto + k] = alert.serialize()
+        return results
 
     def detect(self, parsed: ParserSchema, alert: DetectorSchema) -> bool:
         combo = self._combo(parsed)
@@ -302,6 +426,25 @@ class NewValueComboDetector(CoreDetector):
         alert.description = f"Unknown combination: {combo!r}"
         return True
 
+    # -- data-parallel state merge (dist_mode "dp") --------------------
+    def dist_sync(self, group=None) -> None:
+        """COLLECTIVE union of every rank's learnt combinations, as
+        NewValueDetector.dist_sync unions the value sets."""
+        import torch.distributed as tdist
+
+        if not tdist.is_initialized() or tdist.get_world_size(group) <= 1:
+            return
+        world = tdist.get_world_size(group)
+        local = sorted(self.known_combos, key=repr)
+        gathered: list = [None] * world
+        tdist.all_gather_object(gathered, local, group=group)
+        me = tdist.get_rank(group)
+        for r, other in enumerate(gathered):
+            if r == me or not other:
+                continue
+            for combo in other:
+                self._learn_combo(tuple(combo))
+
     def state_dict(self) -> Dict[str, Any]:
         return {
             "seen_lines": self._seen_lines,
@@ -311,6 +454,6 @@ class NewValueComboDetector(CoreDetector):
     def load_state_dict(self, state: Dict[str, Any]) -> None:
         self._seen_lines = int(state.get("seen_lines", 0))
         for packed in state.get("known_combos") or []:
-            self.known_combos.add(
+            self._learn_combo(
                 tuple(None if x == "\x00" else x for x in packed.split("\x1f"))
             )

@@ -375,7 +375,23 @@ class GpuHashSets:
             return {"type": "gpu", "tables": self.tables.cpu()}
         return {"type": "cpu", "sets": [sorted(s) for s in self.sets]}
 
+    def _check_state_shape(self, state) -> None:
+        """A checkpoint holds one table per watch and per combination; one
+        taken under another configuration must not load (its columns would
+        mean other fields)."""
+        if state["type"] == "gpu":
+            theirs = tuple(state["tables"].shape)
+        else:  # CPU sets carry no capacity
+            theirs = (len(state["sets"]), self.capacity)
+        mine = (self.W, self.capacity)
+        if theirs != mine:
+            raise ValueError(
+                f"hash-set checkpoint holds [tables, capacity] = {list(theirs)} "
+                f"but this instance is configured for {list(mine)} "
+                "(watches + combos, hashset_capacity)")
+
     def load_state_dict(self, state):
+        self._check_state_shape(state)
         if self.device.type == "cuda":
             if state["type"] == "gpu":
                 self.tables.copy_(state["tables"].to(self.device))
@@ -442,3 +458,126 @@ def watch_hashes(lines, match: dict, specs: torch.Tensor, lower: bool = False) -
             match["fmt_caps"], match["n_fmt_caps"], specs, lower,
         )
     return watch_hashes_cpu(lines, match, specs, lower)
+
+
+# ---------------------------------------------------------------------------
+# detector: combinations of watched fields (docs/kernels.md, "Combination
+# hash" is the definition; the kernel, the CPU mirror and combo_fold below
+# are its three implementations)
+# ---------------------------------------------------------------------------
+
+FNV_OFFSET = 1469598103934665603
+FNV_PRIME = 1099511628211
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _as_i64(h: int) -> int:
+    """Two's-complement view of an unsigned 64-bit hash (tensors are int64)."""
+    return h - (1 << 64) if h >= (1 << 63) else h
+
+
+def watch_spec_row(w: dict) -> List[int]:
+    """One watch dict -> the kernel's WatchSpec row (kind, event, pos, pad)."""
+    kind = 0 if w.get("kind", "variable") == "variable" else 1
+    return [kind, int(w.get("event", -1)), int(w["pos"]), 0]
+
+
+def pack_combos(combos: Sequence[Sequence[dict]]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """List of combinations, each a list of watch dicts -> (members int32
+    [M, 4], combo_off int32 [C + 1]), CSR style. This is the host-side
+    validation of the offsets the kernel trusts: they start at 0, strictly
+    increase (no empty combination) and end at M."""
+    rows: List[List[int]] = []
+    off = [0]
+    for c, combo in enumerate(combos):
+        if len(combo) == 0:
+            raise ValueError(f"combo {c} is empty: a combination needs at least one member")
+        for j, w in enumerate(combo):
+            if "pos" not in w:
+                raise ValueError(f"combo {c}, member {j} has no 'pos': {dict(w)!r}")
+            row = watch_spec_row(w)
+            if row[2] < 0:
+                raise ValueError(f"combo {c}, member {j}: 'pos' must be >= 0, got {row[2]}")
+            rows.append(row)
+        off.append(len(rows))
+    members = (torch.tensor(rows, dtype=torch.int32) if rows
+               else torch.zeros((0, 4), dtype=torch.int32))
+    return members, torch.tensor(off, dtype=torch.int32)
+
+
+def combo_fold(relevant, member_hashes):
+    """Host fold of the combination hash, vectorised over a batch.
+
+    relevant [B, n] (0/1) and member_hashes [B, n] (int64 or uint64, 0 where
+    the member is absent or not relevant) -> int64 numpy array [B]: 0 where
+    no member is relevant, odd otherwise."""
+    import numpy as np
+
+    r = np.asarray(relevant)
+    m = np.asarray(member_hashes)
+    if r.ndim != 2 or r.shape != m.shape:
+        raise ValueError(
+            f"relevant {r.shape} and member_hashes {m.shape} must be the same [B, n]")
+    r = (r != 0).astype(np.uint64)
+    m = m.astype(np.int64, copy=False).view(np.uint64) if m.dtype != np.uint64 else m
+    m = np.where(r != 0, m, np.uint64(0))
+    prime = np.uint64(FNV_PRIME)
+    h = np.full(r.shape[0], FNV_OFFSET, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        for j in range(r.shape[1]):
+            h = (h ^ r[:, j]) * prime
+            for b in range(8):
+                h = (h ^ ((m[:, j] >> np.uint64(8 * b)) & np.uint64(0xFF))) * prime
+    h = np.where(r.any(axis=1), h | np.uint64(1), np.uint64(0))
+    return h.view(np.int64)
+
+
+def watch_combo_hashes_cpu(
+    lines: torch.Tensor,
+    match: dict,
+    specs: torch.Tensor,
+    members: torch.Tensor,
+    combo_off: torch.Tensor,
+    lower: bool = False,
+) -> torch.Tensor:
+    """CPU mirror of dmx_watch_combo_hashes: int64 [B, W + C], plain Python
+    integers throughout."""
+    B = lines.shape[0]
+    W = specs.shape[0]
+    off = [int(x) for x in combo_off.tolist()]
+    C = len(off) - 1
+    out = torch.zeros((B, W + C), dtype=torch.int64)
+    out[:, :W] = watch_hashes_cpu(lines, match, specs, lower)
+    if C == 0 or B == 0:
+        return out
+    # each member's span hash as an unsigned value (0 = absent / not relevant)
+    mh = watch_hashes_cpu(lines, match, members, lower).tolist()
+    mem = members.tolist()
+    ev = match["event_id"].tolist()
+    for i in range(B):
+        for c in range(C):
+            h, any_relevant = FNV_OFFSET, False
+            for j in range(off[c], off[c + 1]):
+                kind, event = mem[j][0], mem[j][1]
+                r = 1 if (kind != 0 or event < 0 or ev[i] == event) else 0
+                any_relevant = any_relevant or bool(r)
+                m = mh[i][j] & _U64
+                h = ((h ^ r) * FNV_PRIME) & _U64
+                for b in range(8):
+                    h = ((h ^ ((m >> (8 * b)) & 0xFF)) * FNV_PRIME) & _U64
+            out[i, W + c] = _as_i64(h | 1) if any_relevant else 0
+    return out
+
+
+def watch_combo_hashes(
+    lines, match: dict, specs: torch.Tensor, members: torch.Tensor,
+    combo_off: torch.Tensor, lower: bool = False,
+) -> torch.Tensor:
+    """Watch hashes and combination hashes of a parsed batch, [B, W + C]."""
+    if lines.is_cuda:
+        return _require_ext().watch_combo_hashes(
+            lines, match["event_id"], match["caps"], match["n_caps"],
+            match["fmt_caps"], match["n_fmt_caps"], specs, members, combo_off,
+            lower,
+        )
+    return watch_combo_hashes_cpu(lines, match, specs, members, combo_off, lower)

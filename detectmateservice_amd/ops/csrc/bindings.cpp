@@ -498,12 +498,22 @@ torch::Tensor edit_distance(torch::Tensor A, torch::Tensor a_len,
   return dist;
 }
 
-torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
-                           torch::Tensor caps, torch::Tensor n_caps,
-                           torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
-                           torch::Tensor specs, bool lower) {
+// A [n, 4] int32 table of watch specs (kind, event, pos, pad).
+void check_specs(const torch::Tensor& t, const char* name, const char* rows) {
+  check_arg(t, name, torch::kInt32, 2);
+  TORCH_CHECK(t.size(1) == 4, name, " must be int32 [", rows,
+              ", 4] (kind, event, pos, pad), got ", t.sizes());
+}
+
+// The parsed batch that both watch-hash entry points read.
+void check_watch_args(const torch::Tensor& lines,
+                      const torch::Tensor& event_id, const torch::Tensor& caps,
+                      const torch::Tensor& n_caps,
+                      const torch::Tensor& fmt_caps,
+                      const torch::Tensor& n_fmt_caps,
+                      const torch::Tensor& specs) {
   check_arg(lines, "lines", torch::kUInt8, 2);
-  const auto B = lines.size(0), max_len = lines.size(1);
+  const auto B = lines.size(0);
   check_arg(event_id, "event_id", torch::kInt32, 1);
   check_numel(event_id, "event_id", B, "B");
   check_caps(caps, "caps", B);
@@ -512,10 +522,15 @@ torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
   check_caps(fmt_caps, "fmt_caps", B);
   check_arg(n_fmt_caps, "n_fmt_caps", torch::kInt32, 1);
   check_numel(n_fmt_caps, "n_fmt_caps", B, "B");
-  check_arg(specs, "specs", torch::kInt32, 2);
-  TORCH_CHECK(specs.size(1) == 4,
-              "specs must be int32 [W, 4] (kind, event, pos, pad), got ",
-              specs.sizes());
+  check_specs(specs, "specs", "W");
+}
+
+torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
+                           torch::Tensor caps, torch::Tensor n_caps,
+                           torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
+                           torch::Tensor specs, bool lower) {
+  check_watch_args(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps, specs);
+  const auto B = lines.size(0), max_len = lines.size(1);
   const auto W = specs.size(0);
   DeviceScope dev({{"lines", lines},
                    {"event_id", event_id},
@@ -532,6 +547,63 @@ torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
       fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
       (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)W, (int)B,
       lower ? 1 : 0, hashes.data_ptr<int64_t>(), dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return hashes;
+}
+
+// Watches and combinations in one launch: hashes [B, W + C]. The offsets'
+// VALUES (start at 0, non-decreasing, no empty combination, end at M) are
+// what ops.pack_combos guarantees before upload; this binding checks them
+// only when combo_off is host-resident, where reading them is free, and
+// never reads a device tensor. On device it checks what the shapes show
+// (M >= C), and the kernel clamps each member range into [0, M].
+torch::Tensor watch_combo_hashes(torch::Tensor lines, torch::Tensor event_id,
+                                 torch::Tensor caps, torch::Tensor n_caps,
+                                 torch::Tensor fmt_caps,
+                                 torch::Tensor n_fmt_caps, torch::Tensor specs,
+                                 torch::Tensor members,
+                                 torch::Tensor combo_off, bool lower) {
+  check_watch_args(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps, specs);
+  const auto B = lines.size(0), max_len = lines.size(1);
+  const auto W = specs.size(0);
+  check_specs(members, "members", "M");
+  const auto M = members.size(0);
+  check_arg(combo_off, "combo_off", torch::kInt32, 1);
+  TORCH_CHECK(combo_off.numel() >= 1,
+              "combo_off must hold at least one offset (C + 1 of them)");
+  const auto C = combo_off.numel() - 1;
+  TORCH_CHECK(M >= C, "combo_off: ", C, " combinations need at least ", C,
+              " members (none may be empty), members has M = ", M);
+  if (combo_off.is_cpu()) {
+    const int32_t* off = combo_off.data_ptr<int32_t>();
+    TORCH_CHECK(off[0] == 0, "combo_off must start at 0, got ", off[0]);
+    for (int64_t c = 0; c < C; ++c)
+      TORCH_CHECK(off[c + 1] > off[c], "combo_off: combination ", c,
+                  " is empty or its offsets decrease (", off[c], " .. ",
+                  off[c + 1], ")");
+    TORCH_CHECK(off[C] == M, "combo_off must end at M = ", M,
+                " (rows of members), got ", off[C]);
+  }
+  TORCH_CHECK(B * (W + C) < (int64_t(1) << 31), "lines: B * (W + C) = ", B,
+              " * ", W + C, " must be below 2^31 (the kernel's flat index)");
+  DeviceScope dev({{"lines", lines},
+                   {"event_id", event_id},
+                   {"caps", caps},
+                   {"n_caps", n_caps},
+                   {"fmt_caps", fmt_caps},
+                   {"n_fmt_caps", n_fmt_caps},
+                   {"specs", specs},
+                   {"members", members},
+                   {"combo_off", combo_off}});
+  auto hashes = torch::zeros({B, W + C}, lines.options().dtype(torch::kInt64));
+  if (B == 0 || W + C == 0) return hashes;
+  dmx_launch_watch_combo_hashes(
+      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
+      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
+      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
+      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)W,
+      members.data_ptr<int32_t>(), (int)M, combo_off.data_ptr<int32_t>(),
+      (int)C, (int)B, lower ? 1 : 0, hashes.data_ptr<int64_t>(), dev.stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return hashes;
 }
@@ -607,6 +679,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "geometry, blob sizes and named offsets of the fused BERT kernel");
   m.def("template_match", &template_match, "batched wildcard template match");
   m.def("watch_hashes", &watch_hashes, "hash watched capture spans");
+  m.def("watch_combo_hashes", &watch_combo_hashes,
+        "hash watched capture spans and field combinations, [B, W + C]");
   m.def("hashset_insert", &hashset_insert, "insert hashes into GPU sets");
   m.def("hashset_probe", &hashset_probe, "probe hashes against GPU sets");
   m.def("edit_distance", &edit_distance,

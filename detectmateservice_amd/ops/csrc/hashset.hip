@@ -73,6 +73,96 @@ void dmx_watch_hashes(
   hashes[idx] = h;
 }
 
+// Whether spec `s` applies to a line of event `event`: a header variable
+// always does, a content variable when it is scoped to no event or to this one.
+static __device__ __forceinline__ int watch_relevant(const WatchSpec s,
+                                                     int event) {
+  return s.kind != 0 || s.event < 0 || event == s.event;
+}
+
+// Hash of the span that spec `s` watches on `line`: 0 when the spec is not
+// relevant for the line or the field is absent. The same lookup as in
+// dmx_watch_hashes, which keeps its own copy: routed through this helper it
+// compiles to two more scalar instructions, and the watches-only path is
+// kept instruction for instruction what it was.
+static __device__ __forceinline__ unsigned long long watch_span_hash(
+    const WatchSpec s, int line,
+    const unsigned char* __restrict__ lines, int max_len,
+    const int* __restrict__ event_id,
+    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
+    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
+    int max_fmt_caps, int lower) {
+  unsigned long long h = 0ull;
+  int start = -1, end = -1;
+  if (s.kind == 0) {
+    if ((s.event < 0 || event_id[line] == s.event) && s.pos < n_caps[line]) {
+      start = caps[((long)line * max_caps + s.pos) * 2];
+      end = caps[((long)line * max_caps + s.pos) * 2 + 1];
+    }
+  } else {
+    if (n_fmt_caps && s.pos < n_fmt_caps[line]) {
+      start = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2];
+      end = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2 + 1];
+    }
+  }
+  if (start >= 0 && end >= start)
+    h = fnv1a64(lines + (long)line * max_len + start, end - start, lower);
+  return h;
+}
+
+// Watches and combinations in one launch. For each (line, column) of
+// [B, W + C]: columns < W are dmx_watch_hashes' columns; column W + c is
+// the hash of combination c (docs/kernels.md, "Combination hash"): every
+// member's relevance bit and the 8 bytes of its span hash, low byte first,
+// folded FNV-1a style in member order and forced odd, or 0 when no member
+// is relevant for the line. members [M, 4] holds WatchSpec rows, combo c
+// owns rows combo_off[c] .. combo_off[c + 1]; the host guarantees offsets
+// in [0, M] (ops.pack_combos), the clamp keeps a broken promise in bounds.
+extern "C" __global__ __launch_bounds__(256)
+void dmx_watch_combo_hashes(
+    const unsigned char* __restrict__ lines, int max_len,
+    const int* __restrict__ event_id,
+    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
+    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
+    int max_fmt_caps,
+    const WatchSpec* __restrict__ specs, int W,
+    const WatchSpec* __restrict__ members, int M,
+    const int* __restrict__ combo_off, int C,
+    int B, int lower,
+    unsigned long long* __restrict__ hashes) {  // [B, W + C]
+  const int cols = W + C;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)B * cols) return;
+  const int idx = (int)gid;
+  const int line = idx / cols;
+  const int col = idx % cols;
+  if (col < W) {
+    hashes[idx] = watch_span_hash(specs[col], line, lines, max_len, event_id,
+                                  caps, n_caps, max_caps, fmt_caps, n_fmt_caps,
+                                  max_fmt_caps, lower);
+    return;
+  }
+  const int event = event_id[line];
+  const int m0 = max(combo_off[col - W], 0);
+  const int m1 = min(combo_off[col - W + 1], M);
+  unsigned long long h = 1469598103934665603ull;
+  int any = 0;
+  for (int m = m0; m < m1; ++m) {
+    const WatchSpec s = members[m];
+    const int relevant = watch_relevant(s, event);
+    unsigned long long mh = watch_span_hash(
+        s, line, lines, max_len, event_id, caps, n_caps, max_caps, fmt_caps,
+        n_fmt_caps, max_fmt_caps, lower);
+    any |= relevant;
+    h = (h ^ (unsigned long long)relevant) * 1099511628211ull;
+    for (int b = 0; b < 8; ++b) {
+      h = (h ^ (mh & 0xffull)) * 1099511628211ull;
+      mh >>= 8;
+    }
+  }
+  hashes[idx] = any ? (h | 1ull) : 0ull;
+}
+
 extern "C" __global__ __launch_bounds__(256)
 void dmx_hashset_insert(
     const unsigned long long* __restrict__ hashes,  // [B, W]
@@ -132,6 +222,22 @@ extern "C" void dmx_launch_watch_hashes(
                      fmt_caps, n_fmt_caps, max_fmt_caps,
                      (const WatchSpec*)specs, W, B, lower,
                      (unsigned long long*)hashes);
+}
+
+extern "C" void dmx_launch_watch_combo_hashes(
+    const uint8_t* lines, int max_len, const int32_t* event_id,
+    const int32_t* caps, const int32_t* n_caps, int max_caps,
+    const int32_t* fmt_caps, const int32_t* n_fmt_caps, int max_fmt_caps,
+    const int32_t* specs, int W, const int32_t* members, int M,
+    const int32_t* combo_off, int C, int B, int lower, int64_t* hashes,
+    hipStream_t stream) {
+  const long total = (long)B * (W + C);
+  const int grid = (int)((total + 255) / 256);
+  hipLaunchKernelGGL(dmx_watch_combo_hashes, dim3(grid), dim3(256), 0, stream,
+                     lines, max_len, event_id, caps, n_caps, max_caps,
+                     fmt_caps, n_fmt_caps, max_fmt_caps,
+                     (const WatchSpec*)specs, W, (const WatchSpec*)members, M,
+                     combo_off, C, B, lower, (unsigned long long*)hashes);
 }
 
 extern "C" void dmx_launch_hashset_insert(

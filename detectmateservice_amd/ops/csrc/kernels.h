@@ -163,6 +163,19 @@ void dmx_launch_watch_hashes(const uint8_t* lines, int max_len,
                              const int32_t* n_fmt_caps, int max_fmt_caps,
                              const int32_t* specs, int W, int B, int lower,
                              int64_t* hashes, hipStream_t stream);
+// hashes [B, W + C]: the W watch columns, then one column per combination.
+// members: [M, 4] int32 rows laid out like specs; combo_off: [C + 1] int32,
+// combination c owns member rows combo_off[c] .. combo_off[c + 1].
+void dmx_launch_watch_combo_hashes(const uint8_t* lines, int max_len,
+                                   const int32_t* event_id,
+                                   const int32_t* caps, const int32_t* n_caps,
+                                   int max_caps, const int32_t* fmt_caps,
+                                   const int32_t* n_fmt_caps,
+                                   int max_fmt_caps, const int32_t* specs,
+                                   int W, const int32_t* members, int M,
+                                   const int32_t* combo_off, int C, int B,
+                                   int lower, int64_t* hashes,
+                                   hipStream_t stream);
 void dmx_launch_hashset_insert(const int64_t* hashes, int64_t* tables, int B,
                                int W, int capacity, hipStream_t stream);
 void dmx_launch_hashset_probe(const int64_t* hashes, const int64_t* tables,

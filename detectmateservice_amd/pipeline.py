@@ -12,9 +12,12 @@ Stage structure per batch (all on `device`):
   1. template_match kernel: log_format header split + template match
      (event_id + capture spans)
   2. NewValue watch: hash watched spans (kernel) -> probe GPU hash sets
-     (training batches insert instead)
+     (training batches insert instead). With ``combos`` configured the same
+     launch also hashes each combination of fields (docs/kernels.md,
+     "Combination hash") and the same probe covers watches and combos.
   3. Transformer scorer (BERT-tiny bf16 MFMA) over content-span byte tokens
-Anomaly = NewValue unseen-value hit OR transformer score > threshold.
+Anomaly = NewValue unseen-value hit OR unseen combination OR transformer
+score > threshold.
 
 ``score_mode`` says what the transformer score is. ``"head"`` (default) is
 the model's linear score head. ``"embedding"`` is the distance of the line's
@@ -50,6 +53,10 @@ class PipelineConfig:
     #: watched fields: list of dicts {kind: "variable"|"header", pos: int,
     #: event: int (-1 = any)} — mirrors NewValueDetector specs
     watches: Sequence[dict] = ()
+    #: watched combinations: each a list of members written like `watches`
+    #: entries; a line alerts when the tuple of its member values is new
+    #: (NewValueComboDetector). hashset_capacity applies per combination.
+    combos: Sequence[Sequence[dict]] = ()
     hashset_capacity: int = 1 << 16
     #: transformer detector on/off + threshold
     use_transformer: bool = True
@@ -73,18 +80,24 @@ class GpuPipeline:
             device=self.device,
             max_len=config.max_len,
         )
-        specs = []
-        for w in config.watches:
-            kind = 0 if w.get("kind", "variable") == "variable" else 1
-            specs.append([kind, int(w.get("event", -1)), int(w["pos"]), 0])
+        specs = [ops.watch_spec_row(w) for w in config.watches]
         self.specs = (
             torch.tensor(specs, dtype=torch.int32, device=self.device)
             if specs
             else torch.zeros((0, 4), dtype=torch.int32, device=self.device)
         )
+        # combinations: CSR member table, validated on the host before upload
+        self.n_combos = len(config.combos)
+        self.members = self.combo_off = None
+        if self.n_combos:
+            members, combo_off = ops.pack_combos(config.combos)
+            self.members = members.to(self.device)
+            self.combo_off = combo_off.to(self.device)
+        # one table per watch, then one per combination
+        n_tables = len(specs) + self.n_combos
         self.hashsets = (
-            ops.GpuHashSets(len(specs), config.hashset_capacity, device=self.device)
-            if specs
+            ops.GpuHashSets(n_tables, config.hashset_capacity, device=self.device)
+            if n_tables
             else None
         )
         self.model = (
@@ -115,7 +128,8 @@ class GpuPipeline:
         """lines [B, max_len] u8 + lengths on self.device → result tensors.
 
         Returns event_id [B], anomaly [B] (bool), scores [B] (f32, 0 when
-        transformer off), nv_unseen [B, W]."""
+        transformer off), nv_unseen [B, W] (None without watches),
+        combo_unseen [B, C] (None without combos)."""
         B = lines.shape[0]
         if B == 0:
             return {
@@ -123,6 +137,7 @@ class GpuPipeline:
                 "anomaly": torch.zeros(0, dtype=torch.bool, device=lines.device),
                 "scores": torch.zeros(0, dtype=torch.float32, device=lines.device),
                 "nv_unseen": None,
+                "combo_unseen": None,
                 "match": None,
             }
         # roctx-visible stage ranges (torch.cuda.nvtx maps to rocTracer
@@ -138,11 +153,17 @@ class GpuPipeline:
         train_upto = min(B, n_train_left)
         self.seen_lines += B
 
-        nv_unseen = None
+        nv_unseen = None  # here [B, W + C]; split into its two views below
+        W = self.specs.shape[0]
         if _rng:
             torch.cuda.nvtx.range_push("dmx::new_value")
-        if self.hashsets is not None and self.specs.shape[0] > 0:
-            hashes = ops.watch_hashes(lines, match, self.specs, self.config.lowercase)
+        if self.hashsets is not None:
+            if self.n_combos:
+                hashes = ops.watch_combo_hashes(
+                    lines, match, self.specs, self.members, self.combo_off,
+                    self.config.lowercase)
+            else:
+                hashes = ops.watch_hashes(lines, match, self.specs, self.config.lowercase)
             if train_upto > 0:
                 self.hashsets.insert(hashes[:train_upto])
             if train_upto == 0:
@@ -152,12 +173,12 @@ class GpuPipeline:
             elif train_upto < B:
                 unseen_tail = self.hashsets.probe(hashes[train_upto:])
                 nv_unseen = torch.zeros(
-                    (B, self.specs.shape[0]), dtype=torch.int32, device=lines.device
+                    (B, W + self.n_combos), dtype=torch.int32, device=lines.device
                 )
                 nv_unseen[train_upto:] = unseen_tail
             else:
                 nv_unseen = torch.zeros(
-                    (B, self.specs.shape[0]), dtype=torch.int32, device=lines.device
+                    (B, W + self.n_combos), dtype=torch.int32, device=lines.device
                 )
 
         if _rng:
@@ -180,13 +201,19 @@ class GpuPipeline:
             torch.cuda.nvtx.range_pop()
 
         anomaly = scores > self.config.score_threshold
+        combo_unseen = None
         if nv_unseen is not None:
+            # one reduction over watch and combination columns alike
             anomaly = anomaly | (nv_unseen.sum(dim=1) > 0)
+            if self.n_combos:
+                combo_unseen = nv_unseen[:, W:]
+                nv_unseen = nv_unseen[:, :W] if W else None
         return {
             "event_id": match["event_id"],
             "anomaly": anomaly,
             "scores": scores,
             "nv_unseen": nv_unseen,
+            "combo_unseen": combo_unseen,
             "match": match,
         }
 
