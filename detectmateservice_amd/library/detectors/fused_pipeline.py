@@ -43,6 +43,11 @@ class FusedPipelineDetectorConfig(CoreConfig):
     #: Gaussian fitted to the embeddings of the data_use_training rows.
     score_mode: str = "head"
     data_use_training: int = 0
+    #: event-rate windows: {window_lines, ewma_alpha, z_threshold,
+    #: min_windows}, FrequencyDetector's keys and defaults ({} = defaults).
+    #: The line that completes a window alerts when an event's count in it
+    #: is z_threshold sigmas off its EWMA baseline. None = off.
+    event_rate: Optional[Dict[str, Any]] = None
     device: Optional[str] = None
     seed: int = 1234
     #: capture the detect path as ONE hipGraph at this batch size (0 = off).
@@ -81,6 +86,8 @@ class FusedPipelineDetector(CoreComponent):
                 score_threshold=cfg.score_threshold,
                 score_mode=cfg.score_mode,
                 train_lines=cfg.data_use_training,
+                event_rate=(dict(cfg.event_rate)
+                            if cfg.event_rate is not None else None),
                 seed=cfg.seed,
             ),
             device=self.device,
@@ -116,7 +123,9 @@ class FusedPipelineDetector(CoreComponent):
         """Re-score the newest ``lines_back`` resident lines of the HBM
         line buffer — post-hoc analysis with a NEW threshold (or model
         state) at HBM bandwidth, the config-5 use case. Returns summary
-        counts (the alert path stays with the live stream)."""
+        counts (the alert path stays with the live stream). The event-rate
+        stage is skipped: old lines belong to no window of the live stream,
+        so its state stays as it is and no rate alert is counted."""
         if self.line_buffer is None:
             return {"rescored": 0, "reason": "line buffer disabled"}
         lines, lens = self.line_buffer.window(lines_back)
@@ -130,7 +139,7 @@ class FusedPipelineDetector(CoreComponent):
             # force detect mode: a rescore during the training phase must
             # not INSERT window values into the live hash sets
             self.pipe.seen_lines = max(seen, self.pipe.config.train_lines)
-            out = self.pipe.process_packed(lines, lens)
+            out = self.pipe.process_packed(lines, lens, rate=False)
         finally:
             self.pipe.seen_lines = seen
             self.pipe.config.score_threshold = old_thr
@@ -173,6 +182,8 @@ class FusedPipelineDetector(CoreComponent):
         nv = out["nv_unseen"].cpu() if out["nv_unseen"] is not None else None
         combo = out.get("combo_unseen")
         combo = combo.cpu() if combo is not None else None
+        rate_hits = out.get("rate_hits")
+        rate_hits = rate_hits.cpu() if rate_hits is not None else None
         now = int(time.time())
         alerts = []
         for i in idxs:
@@ -181,6 +192,8 @@ class FusedPipelineDetector(CoreComponent):
                 reasons.append("unknown watched value")
             if combo is not None and int(combo[i].sum()) > 0:
                 reasons.append("unknown combination")
+            if rate_hits is not None and int(rate_hits[i]) > 0:
+                reasons.append(self._rate_reason(out, i))
             if (self.pipe.model is not None
                     and float(scores[i]) > self.config.score_threshold):
                 what = ("embedding distance"
@@ -197,6 +210,19 @@ class FusedPipelineDetector(CoreComponent):
                 description="Anomaly: " + "; ".join(reasons),
             ).serialize()))
         return alerts
+
+    @staticmethod
+    def _rate_reason(out, i: int) -> str:
+        """"event rate: event 3: 950/window (z=+12.3); ..." for boundary row
+        i: the flagged bins of the window that row completed."""
+        slot = int(out["rate_slot"][i])
+        counts = out["rate_counts"][slot].cpu()
+        z = out["rate_z"][slot].cpu()
+        parts = []
+        for e in torch.nonzero(z, as_tuple=False).flatten().tolist():
+            who = "unparsed" if e == 0 else f"event {e}"
+            parts.append(f"{who}: {int(counts[e])}/window (z={float(z[e]):+.1f})")
+        return "event rate: " + "; ".join(parts)
 
     def process_packed_frames(self, lines, lens, ids_blob, ids_off) -> List:
         """Engine packed-loop entry: tensors in (already decoded by the
@@ -296,7 +322,8 @@ class FusedPipelineDetector(CoreComponent):
     def dist_sync(self, group=None) -> None:
         """COLLECTIVE merge of the data-parallel GPU hash sets (one
         batched insert-kernel call per peer table —
-        parallel/dist.py::all_reduce_hashsets)."""
+        parallel/dist.py::all_reduce_hashsets). Event-rate state is left
+        alone: each rank judges the rate of its own shard of the stream."""
         import torch.distributed as tdist
 
         if not tdist.is_initialized() or tdist.get_world_size(group) <= 1:
@@ -328,6 +355,8 @@ class FusedPipelineDetector(CoreComponent):
             state["model"] = self.pipe.model.state_dict()
         if self.pipe.embedding_stats is not None:
             state["embedding_stats"] = self.pipe.embedding_stats.state_dict()
+        if self.pipe.event_rate is not None:
+            state["event_rate"] = self.pipe.event_rate.state_dict()
         return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
@@ -338,3 +367,5 @@ class FusedPipelineDetector(CoreComponent):
             self.pipe.model.load_state_dict(state["model"])
         if "embedding_stats" in state and self.pipe.embedding_stats is not None:
             self.pipe.embedding_stats.load_state_dict(state["embedding_stats"])
+        if "event_rate" in state and self.pipe.event_rate is not None:
+            self.pipe.event_rate.load_state_dict(state["event_rate"])

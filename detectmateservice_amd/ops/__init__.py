@@ -581,3 +581,207 @@ def watch_combo_hashes(
             lower,
         )
     return watch_combo_hashes_cpu(lines, match, specs, members, combo_off, lower)
+
+
+# ---------------------------------------------------------------------------
+# detector: event-rate windows (docs/kernels.md, "Event-rate windows" is the
+# definition; event_rate.hip and event_rate_step_cpu below implement it)
+# ---------------------------------------------------------------------------
+
+#: kernels.h limits, repeated here so that a CPU-only install can refuse a
+#: configuration the GPU could not run (tests compare them to the extension's)
+ER_MAX_EVENTS = 8192
+ER_MAX_CELLS = 1 << 24
+
+#: FrequencyDetectorConfig's keys and defaults
+EVENT_RATE_DEFAULTS = {
+    "window_lines": 1000,
+    "ewma_alpha": 0.3,
+    "z_threshold": 4.0,
+    "min_windows": 3,
+}
+
+
+def event_rate_slots(B: int, window_lines: int) -> int:
+    """Window slots of one call: B lines on top of an open window complete
+    at most B // L + 1 windows and leave one open."""
+    return B // int(window_lines) + 2
+
+
+def _check_event_rate_params(window_lines, ewma_alpha, z_threshold, min_windows) -> None:
+    if not 1 <= int(window_lines) <= 2**31 - 1:
+        raise ValueError(f"window_lines must be within 1 .. 2^31 - 1, got {window_lines}")
+    if not 0.0 < float(ewma_alpha) <= 1.0:
+        raise ValueError(f"ewma_alpha must be in (0, 1], got {ewma_alpha}")
+    if not float(z_threshold) >= 0.0:
+        raise ValueError(f"z_threshold must be >= 0, got {z_threshold}")
+    if not 0 <= int(min_windows) <= 2**31 - 1:
+        raise ValueError(f"min_windows must be within 0 .. 2^31 - 1, got {min_windows}")
+
+
+def event_rate_step_cpu(
+    event_id: torch.Tensor,
+    n_valid,
+    mean: torch.Tensor,
+    var: torch.Tensor,
+    known: torch.Tensor,
+    open_counts: torch.Tensor,
+    ctl: torch.Tensor,
+    train_upto: int,
+    window_lines: int,
+    ewma_alpha: float,
+    z_threshold: float,
+    min_windows: int,
+):
+    """CPU mirror of ``_dmx_C.event_rate_step``: same arguments, the state
+    tensors (mean, var f64 [E]; known, open_counts int32 [E]; ctl int32 [2])
+    updated in place, same outputs (rate_counts int32 [NW, E], rate_z f64
+    [NW, E], rate_hits int32 [B], rate_slot int32 [B]). numpy f64, one
+    rounding per operation, in the order docs/kernels.md gives."""
+    import numpy as np
+
+    _check_event_rate_params(window_lines, ewma_alpha, z_threshold, min_windows)
+    B, E, L = int(event_id.shape[0]), int(mean.shape[0]), int(window_lines)
+    if not 1 <= E <= ER_MAX_EVENTS:
+        raise ValueError(f"mean: E = {E} bins must be within 1 .. {ER_MAX_EVENTS}")
+    for name, t in (("var", var), ("known", known), ("open_counts", open_counts)):
+        if tuple(t.shape) != (E,):
+            raise ValueError(f"{name} must hold E = {E} elements, got {list(t.shape)}")
+    if not 0 <= int(train_upto) <= B:
+        raise ValueError(f"train_upto must be within 0 .. B = {B}, got {train_upto}")
+    NW = event_rate_slots(B, L)
+    if NW * E > ER_MAX_CELLS:
+        raise ValueError(f"NW * E = {NW} * {E} must not exceed {ER_MAX_CELLS}")
+    z_out = np.zeros((NW, E), dtype=np.float64)
+    hits = np.zeros(B, dtype=np.int32)
+    slot = np.full(B, -1, dtype=np.int32)
+    if B == 0:
+        return (torch.zeros((NW, E), dtype=torch.int32), torch.from_numpy(z_out),
+                torch.from_numpy(hits), torch.from_numpy(slot))
+
+    m, v = mean.numpy(), var.numpy()  # views: the state is updated in place
+    kn, oc, ct = known.numpy(), open_counts.numpy(), ctl.numpy()
+    n = min(max(int(n_valid), 0), B)
+    p = min(max(int(ct[0]), 0), L - 1)
+    windows_seen = int(ct[1])
+    a = float(ewma_alpha)
+    one_minus_a = 1.0 - a
+
+    ev = event_id.numpy()[:n].astype(np.int64)
+    bins = np.where(ev < 0, 0, ev)
+    counted = (ev != 0) & (bins < E)
+    slot_of = (p + np.arange(n, dtype=np.int64)) // L
+    counts = np.bincount(slot_of[counted] * E + bins[counted], minlength=NW * E)
+    counts = counts.reshape(NW, E).astype(np.int32)
+    counts[0] += oc
+
+    nc = min((p + n) // L, NW - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s in range(nc):
+            boundary = (s + 1) * L - p - 1
+            slot[boundary] = s
+            report = boundary >= train_upto and windows_seen + s >= min_windows
+            c = counts[s].astype(np.float64)
+            k = kn != 0
+            z = (c - m) / np.sqrt(np.maximum(v, 1.0))
+            flag = k & (np.abs(z) > z_threshold) & report
+            d = c - m
+            first = ~k & (c > 0)
+            new_m = a * c + one_minus_a * m
+            new_v = a * (d * d) + one_minus_a * v
+            m[:] = np.where(k, new_m, np.where(first, c, m))
+            v[:] = np.where(k, new_v, np.where(first, np.maximum(c, 1.0), v))
+            kn[first] = 1
+            z_out[s] = np.where(flag, z, 0.0)
+            hits[boundary] = int(flag.sum())
+    oc[:] = counts[nc]
+    ct[0] = (p + n) % L
+    ct[1] = windows_seen + nc
+    return (torch.from_numpy(counts), torch.from_numpy(z_out),
+            torch.from_numpy(hits), torch.from_numpy(slot))
+
+
+def event_rate_step(event_id, n_valid, mean, var, known, open_counts, ctl,
+                    train_upto, window_lines, ewma_alpha, z_threshold, min_windows):
+    """One batch of the event-rate stage on event_id's device."""
+    fn = _require_ext().event_rate_step if event_id.is_cuda else event_rate_step_cpu
+    return fn(event_id, n_valid, mean, var, known, open_counts, ctl,
+              int(train_upto), int(window_lines), float(ewma_alpha),
+              float(z_threshold), int(min_windows))
+
+
+class EventRateState:
+    """Per-stream state of the event-rate stage, resident on ``device``: the
+    EWMA baseline (``mean``, ``var`` f64 [E]), ``known`` and the open
+    window's ``open_counts`` (int32 [E]) and ``ctl`` = (in_window,
+    windows_seen), for E = n_templates + 1 bins (bin 0 = unparsed lines).
+    ``step`` advances it by one batch without a host read, so it can be
+    captured into a hipGraph; restoring a checkpoint writes into the same
+    tensors, which a captured graph keeps reading."""
+
+    def __init__(self, n_templates: int, window_lines: int = 1000,
+                 ewma_alpha: float = 0.3, z_threshold: float = 4.0,
+                 min_windows: int = 3, device="cpu") -> None:
+        _check_event_rate_params(window_lines, ewma_alpha, z_threshold, min_windows)
+        if not 0 <= int(n_templates) <= ER_MAX_EVENTS - 1:
+            raise ValueError(
+                f"event_rate supports at most ER_MAX_EVENTS - 1 = {ER_MAX_EVENTS - 1} "
+                f"templates, got {n_templates}")
+        self.E = int(n_templates) + 1
+        self.window_lines = int(window_lines)
+        self.ewma_alpha = float(ewma_alpha)
+        self.z_threshold = float(z_threshold)
+        self.min_windows = int(min_windows)
+        self.device = torch.device(device)
+        self.mean = torch.zeros(self.E, dtype=torch.float64, device=self.device)
+        self.var = torch.zeros(self.E, dtype=torch.float64, device=self.device)
+        self.known = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        self.open_counts = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        self.ctl = torch.zeros(2, dtype=torch.int32, device=self.device)
+        # the row count handed to the kernels: a device word, rewritten only
+        # when the count changes (a captured graph reads it at replay)
+        self.n_valid = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._n_valid_host = 0
+
+    _STATE = ("mean", "var", "known", "open_counts", "ctl")
+
+    def set_n_valid(self, n: int) -> None:
+        if int(n) != self._n_valid_host:
+            self.n_valid.fill_(int(n))
+            self._n_valid_host = int(n)
+
+    def step(self, event_id: torch.Tensor, n_valid: Optional[int] = None,
+             train_upto: int = 0) -> dict:
+        """Count the first ``n_valid`` rows (default: all) of event_id [B]
+        and roll every window they complete. ``n_valid=None`` inside a graph
+        capture would record the write; callers that capture set it first
+        with set_n_valid()."""
+        self.set_n_valid(event_id.shape[0] if n_valid is None else n_valid)
+        counts, z, hits, slot = event_rate_step(
+            event_id, self.n_valid, self.mean, self.var, self.known,
+            self.open_counts, self.ctl, train_upto, self.window_lines,
+            self.ewma_alpha, self.z_threshold, self.min_windows)
+        return {"rate_counts": counts, "rate_z": z, "rate_hits": hits,
+                "rate_slot": slot}
+
+    def state_dict(self) -> dict:
+        state = {k: getattr(self, k).detach().cpu().clone() for k in self._STATE}
+        state["window_lines"] = self.window_lines
+        return state
+
+    def load_state_dict(self, state: dict) -> None:
+        if int(state["window_lines"]) != self.window_lines:
+            raise ValueError(
+                f"event-rate checkpoint was taken with window_lines = "
+                f"{int(state['window_lines'])} but this instance is configured "
+                f"for {self.window_lines} (its open window would not line up)")
+        for k in self._STATE:
+            mine = getattr(self, k)
+            if tuple(state[k].shape) != tuple(mine.shape):
+                raise ValueError(
+                    f"event-rate checkpoint holds {k} {list(state[k].shape)} but "
+                    f"this instance is configured for {list(mine.shape)} "
+                    "(templates + 1 bins)")
+        for k in self._STATE:
+            mine = getattr(self, k)
+            mine.copy_(state[k].to(mine.dtype))

@@ -645,6 +645,86 @@ torch::Tensor hashset_probe(torch::Tensor hashes, torch::Tensor tables) {
   return unseen;
 }
 
+// ---- event-rate windows (docs/kernels.md, "Event-rate windows") ---------------
+
+py::dict event_rate_limits() {
+  py::dict d;
+  d["max_events"] = ER_MAX_EVENTS;
+  d["max_cells"] = ER_MAX_CELLS;
+  return d;
+}
+
+// One batch of the event-rate stage. The state tensors are updated in
+// place; returns (rate_counts [NW, E], rate_z [NW, E], rate_hits [B],
+// rate_slot [B]). n_valid, in_window and windows_seen stay on the device:
+// nothing here reads a tensor's values.
+std::vector<torch::Tensor> event_rate_step(
+    torch::Tensor event_id, torch::Tensor n_valid, torch::Tensor mean,
+    torch::Tensor var, torch::Tensor known, torch::Tensor open_counts,
+    torch::Tensor ctl, int64_t train_upto, int64_t window_lines,
+    double ewma_alpha, double z_threshold, int64_t min_windows) {
+  check_arg(event_id, "event_id", torch::kInt32, 1);
+  const auto B = event_id.size(0);
+  check_arg(n_valid, "n_valid", torch::kInt32, 1);
+  check_numel(n_valid, "n_valid", 1, "one count");
+  check_arg(mean, "mean", torch::kFloat64, 1);
+  const auto E = mean.size(0);
+  TORCH_CHECK(E >= 1 && E <= ER_MAX_EVENTS, "mean: E = templates + 1 = ", E,
+              " bins must be within 1 .. ER_MAX_EVENTS = ", ER_MAX_EVENTS);
+  check_arg(var, "var", torch::kFloat64, 1);
+  check_same_shape(var, "var", mean, "mean");
+  check_arg(known, "known", torch::kInt32, 1);
+  check_numel(known, "known", E, "E");
+  check_arg(open_counts, "open_counts", torch::kInt32, 1);
+  check_numel(open_counts, "open_counts", E, "E");
+  check_arg(ctl, "ctl", torch::kInt32, 1);
+  check_numel(ctl, "ctl", 2, "(in_window, windows_seen)");
+  TORCH_CHECK(window_lines >= 1 && window_lines <= INT32_MAX,
+              "window_lines must be within 1 .. 2^31 - 1, got ", window_lines);
+  TORCH_CHECK(ewma_alpha > 0.0 && ewma_alpha <= 1.0,
+              "ewma_alpha must be in (0, 1], got ", ewma_alpha);
+  TORCH_CHECK(z_threshold >= 0.0, "z_threshold must be >= 0, got ",
+              z_threshold);
+  TORCH_CHECK(min_windows >= 0 && min_windows <= INT32_MAX,
+              "min_windows must be within 0 .. 2^31 - 1, got ", min_windows);
+  TORCH_CHECK(train_upto >= 0 && train_upto <= B,
+              "train_upto must be within 0 .. B = ", B, ", got ", train_upto);
+  TORCH_CHECK(B <= INT32_MAX, "event_id: B = ", B, " must be below 2^31");
+  const int64_t NW = er_window_slots(B, window_lines);
+  TORCH_CHECK(NW * E <= ER_MAX_CELLS, "event_id: NW * E = (B / window_lines",
+              " + 2) * E = ", NW, " * ", E, " must not exceed ", ER_MAX_CELLS,
+              " (raise window_lines or lower the batch)");
+  DeviceScope dev({{"event_id", event_id},
+                   {"n_valid", n_valid},
+                   {"mean", mean},
+                   {"var", var},
+                   {"known", known},
+                   {"open_counts", open_counts},
+                   {"ctl", ctl}});
+  const auto i32 = event_id.options();
+  const auto f64 = event_id.options().dtype(torch::kFloat64);
+  if (B == 0)
+    return {torch::zeros({NW, E}, i32), torch::zeros({NW, E}, f64),
+            torch::zeros({0}, i32), torch::zeros({0}, i32)};
+  // every element of the four outputs is written by the two kernels
+  auto rate_counts = torch::empty({NW, E}, i32);
+  auto rate_z = torch::empty({NW, E}, f64);
+  auto rate_hits = torch::empty({B}, i32);
+  auto rate_slot = torch::empty({B}, i32);
+  auto base = torch::empty({NW, E}, f64);  // scratch between the roll's passes
+  dmx_launch_event_rate(
+      event_id.data_ptr<int32_t>(), n_valid.data_ptr<int32_t>(), (int)B,
+      (int)E, (int)window_lines, (int)train_upto, ewma_alpha, z_threshold,
+      (int)min_windows, mean.data_ptr<double>(), var.data_ptr<double>(),
+      known.data_ptr<int32_t>(), open_counts.data_ptr<int32_t>(),
+      ctl.data_ptr<int32_t>(), base.data_ptr<double>(),
+      rate_counts.data_ptr<int32_t>(),
+      rate_z.data_ptr<double>(), rate_hits.data_ptr<int32_t>(),
+      rate_slot.data_ptr<int32_t>(), dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {rate_counts, rate_z, rate_hits, rate_slot};
+}
+
 }  // namespace
 
 void register_codec(py::module_& m);   // codec.cpp
@@ -683,6 +763,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "hash watched capture spans and field combinations, [B, W + C]");
   m.def("hashset_insert", &hashset_insert, "insert hashes into GPU sets");
   m.def("hashset_probe", &hashset_probe, "probe hashes against GPU sets");
+  m.def("event_rate_step", &event_rate_step,
+        "event-rate windows: count one batch, roll the complete windows");
+  m.def("event_rate_limits", &event_rate_limits,
+        "limits of event_rate_step (max_events, max_cells)");
   m.def("edit_distance", &edit_distance,
         "batched Levenshtein distances (wavefront DP in LDS)");
 }

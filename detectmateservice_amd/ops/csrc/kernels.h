@@ -28,6 +28,8 @@ constexpr int ED_MAX_LEN = 256;       // edit_distance: bytes per string
 constexpr int TM_WAVES = 4;           // template_match: lines per workgroup
 constexpr int TM_MAX_LINE = 512;      // template_match: bytes per line
 constexpr int LDS_DEFAULT_LIMIT = 64 * 1024;  // dynamic LDS without opt-in
+constexpr int ER_MAX_EVENTS = 8192;   // event_rate: bins (32 KiB LDS histogram)
+constexpr int64_t ER_MAX_CELLS = int64_t(1) << 24;  // event_rate: NW * E
 
 // Dynamic LDS of dmx_template_match: the segment blob (16-B rounded) plus
 // one staged line per wave. The kernel carves its arena the same way.
@@ -36,6 +38,12 @@ constexpr int tm_seg_lds_bytes(int seg_bytes_len) {
 }
 constexpr size_t tm_lds_bytes(int seg_bytes_len) {
   return tm_seg_lds_bytes(seg_bytes_len) + TM_WAVES * TM_MAX_LINE;
+}
+
+// Window slots of one dmx_event_rate call: B lines on top of an open window
+// of up to L - 1 lines complete at most B / L + 1 windows and leave one open.
+constexpr int er_window_slots(int64_t B, int64_t window_lines) {
+  return (int)(B / window_lines + 2);
 }
 
 // ---- fused BERT-tiny kernel: fixed geometry --------------------------------
@@ -181,6 +189,21 @@ void dmx_launch_hashset_insert(const int64_t* hashes, int64_t* tables, int B,
 void dmx_launch_hashset_probe(const int64_t* hashes, const int64_t* tables,
                               int B, int W, int capacity, int32_t* unseen,
                               hipStream_t stream);
+
+// event_rate.hip: one batch of the event-rate stage (count + roll launches).
+// State, updated in place: mean, var f64 [E]; known, open_counts int32 [E];
+// ctl int32 [2] = in_window, windows_seen. n_valid: device int32 [1].
+// Outputs, NW = er_window_slots(B, window_lines): rate_counts int32 [NW, E],
+// rate_z f64 [NW, E], rate_hits and rate_slot int32 [B]. All fully written.
+// base: f64 [NW, E] scratch of the roll kernel, contents unspecified.
+void dmx_launch_event_rate(const int32_t* event_id, const int32_t* n_valid,
+                           int B, int E, int window_lines, int train_upto,
+                           double ewma_alpha, double z_threshold,
+                           int min_windows, double* mean, double* var,
+                           int32_t* known, int32_t* open_counts, int32_t* ctl,
+                           double* base, int32_t* rate_counts, double* rate_z,
+                           int32_t* rate_hits, int32_t* rate_slot,
+                           hipStream_t stream);
 
 // edit_distance.hip
 void dmx_launch_edit_distance(const uint8_t* A, const int32_t* a_len, int Na,

@@ -16,8 +16,13 @@ Stage structure per batch (all on `device`):
      launch also hashes each combination of fields (docs/kernels.md,
      "Combination hash") and the same probe covers watches and combos.
   3. Transformer scorer (BERT-tiny bf16 MFMA) over content-span byte tokens
+  4. With ``event_rate`` configured: per-event line counts in windows of
+     ``window_lines`` lines against an EWMA baseline (docs/kernels.md,
+     "Event-rate windows"). The only stage whose verdict is about the stream
+     and not about one line: its state lives on the device and the line that
+     completes a window carries the alert.
 Anomaly = NewValue unseen-value hit OR unseen combination OR transformer
-score > threshold.
+score > threshold OR, on a window's boundary line, a flagged event rate.
 
 ``score_mode`` says what the transformer score is. ``"head"`` (default) is
 the model's linear score head. ``"embedding"`` is the distance of the line's
@@ -65,11 +70,20 @@ class PipelineConfig:
     #: Gaussian fitted to the embeddings of the first train_lines rows.
     score_mode: str = "head"
     train_lines: int = 0  # training-phase length (data_use_training)
+    #: event-rate windows (FrequencyDetector's keys and defaults:
+    #: window_lines 1000, ewma_alpha 0.3, z_threshold 4.0, min_windows 3);
+    #: None = stage off, {} = on with the defaults
+    event_rate: Optional[dict] = None
     bert: BertTinyConfig = field(default_factory=BertTinyConfig)
     seed: int = 1234
 
 
 class GpuPipeline:
+    #: event-rate outputs; the last two are per window slot, [NW, E], not per
+    #: line
+    _RATE_KEYS = ("rate_hits", "rate_slot", "rate_counts", "rate_z")
+    _PER_SLOT_KEYS = ("rate_counts", "rate_z")
+
     def __init__(self, config: PipelineConfig, device: str | torch.device = "cpu") -> None:
         self.config = config
         self.device = torch.device(device)
@@ -115,6 +129,16 @@ class GpuPipeline:
             if config.score_mode == "embedding"
             else None
         )
+        self.event_rate: Optional[ops.EventRateState] = None
+        if config.event_rate is not None:
+            unknown = set(config.event_rate) - set(ops.EVENT_RATE_DEFAULTS)
+            if unknown:
+                raise ValueError(
+                    f"unknown event_rate key(s) {sorted(unknown)}; valid keys: "
+                    f"{sorted(ops.EVENT_RATE_DEFAULTS)}")
+            self.event_rate = ops.EventRateState(
+                len(self.matcher.templates), device=self.device,
+                **{**ops.EVENT_RATE_DEFAULTS, **config.event_rate})
         self.seen_lines = 0
         # hipGraph capture state (enable_graph(); steady-state detect only)
         self._graph = None
@@ -123,13 +147,21 @@ class GpuPipeline:
 
     # ------------------------------------------------------------------
     def process_packed(
-        self, lines: torch.Tensor, line_len: torch.Tensor
+        self, lines: torch.Tensor, line_len: torch.Tensor,
+        n_valid: Optional[int] = None, rate: bool = True,
     ) -> Dict[str, torch.Tensor]:
         """lines [B, max_len] u8 + lengths on self.device → result tensors.
 
         Returns event_id [B], anomaly [B] (bool), scores [B] (f32, 0 when
         transformer off), nv_unseen [B, W] (None without watches),
-        combo_unseen [B, C] (None without combos)."""
+        combo_unseen [B, C] (None without combos) and, with event_rate
+        configured, rate_hits [B], rate_slot [B], rate_counts [NW, E] and
+        rate_z [NW, E] (absent otherwise: ``out.get("rate_hits")`` is None).
+
+        ``n_valid`` and ``rate`` concern the event-rate stage alone, the one
+        stage with stream state: only the first n_valid rows (default: all)
+        enter its windows, and ``rate=False`` skips it, so the call neither
+        moves that state nor reports rate alerts (a re-score of old lines)."""
         B = lines.shape[0]
         if B == 0:
             return {
@@ -139,6 +171,8 @@ class GpuPipeline:
                 "nv_unseen": None,
                 "combo_unseen": None,
                 "match": None,
+                **(dict.fromkeys(self._RATE_KEYS)
+                   if self.event_rate is not None else {}),
             }
         # roctx-visible stage ranges (torch.cuda.nvtx maps to rocTracer
         # markers on ROCm — SURVEY.md §5.1 tracing requirement)
@@ -152,6 +186,18 @@ class GpuPipeline:
         n_train_left = max(0, self.config.train_lines - self.seen_lines)
         train_upto = min(B, n_train_left)
         self.seen_lines += B
+
+        # without event_rate the result holds exactly the keys it always
+        # held; with it the four keys are there, None when the stage is
+        # skipped (read them with .get())
+        rate_out = (dict.fromkeys(self._RATE_KEYS)
+                    if self.event_rate is not None else {})
+        if self.event_rate is not None and rate:
+            if _rng:
+                torch.cuda.nvtx.range_push("dmx::event_rate")
+            rate_out = self.event_rate.step(match["event_id"], n_valid, train_upto)
+            if _rng:
+                torch.cuda.nvtx.range_pop()
 
         nv_unseen = None  # here [B, W + C]; split into its two views below
         W = self.specs.shape[0]
@@ -208,6 +254,9 @@ class GpuPipeline:
             if self.n_combos:
                 combo_unseen = nv_unseen[:, W:]
                 nv_unseen = nv_unseen[:, :W] if W else None
+        if rate_out.get("rate_hits") is not None:
+            # non-zero only on a boundary line outside the training phase
+            anomaly = anomaly | (rate_out["rate_hits"] > 0)
         return {
             "event_id": match["event_id"],
             "anomaly": anomaly,
@@ -215,6 +264,7 @@ class GpuPipeline:
             "nv_unseen": nv_unseen,
             "combo_unseen": combo_unseen,
             "match": match,
+            **rate_out,
         }
 
     def _embedding_scores(
@@ -260,14 +310,17 @@ class GpuPipeline:
             (B, self.config.max_len), dtype=torch.uint8, device=self.device
         )
         static_lens = torch.zeros((B,), dtype=torch.int32, device=self.device)
-        # warm up allocator/kernels on the same shapes, then capture
+        # warm up allocator/kernels on the same shapes, then capture. The
+        # event-rate stage reads its row count from a device word: 0 makes
+        # the warm-ups rewrite its state with the values it holds, and the
+        # captured launches read whatever the word holds at replay.
         for _ in range(2):
-            self.process_packed(static_lines, static_lens)
+            self.process_packed(static_lines, static_lens, n_valid=0)
             self.seen_lines -= B  # warmups must not advance stream state
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self.process_packed(static_lines, static_lens)
+            out = self.process_packed(static_lines, static_lens, n_valid=0)
         self.seen_lines -= B
         self._graph = graph
         self._graph_in = (static_lines, static_lens)
@@ -282,6 +335,8 @@ class GpuPipeline:
         sl, sn = self._graph_in
         sl.copy_(lines, non_blocking=True)
         sn.copy_(lens, non_blocking=True)
+        if self.event_rate is not None:
+            self.event_rate.set_n_valid(lines.shape[0])
         self._graph.replay()
         self.seen_lines += lines.shape[0]
         return self._graph_out
@@ -301,6 +356,9 @@ class GpuPipeline:
         sn[:B].copy_(lens, non_blocking=True)
         if B < sn.shape[0]:
             sn[B:].zero_()
+        if self.event_rate is not None:
+            # pad rows parse as unparsed lines; they must not be counted
+            self.event_rate.set_n_valid(B)
         self._graph.replay()
         self.seen_lines += B
 
@@ -311,4 +369,5 @@ class GpuPipeline:
                 return {k: cut(x) for k, x in v.items()}
             return v
 
-        return {k: cut(v) for k, v in self._graph_out.items()}
+        return {k: (v if k in self._PER_SLOT_KEYS else cut(v))
+                for k, v in self._graph_out.items()}

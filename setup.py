@@ -28,6 +28,7 @@ sources = [
     str(CSRC / "bert_fused.hip"),
     str(CSRC / "template_match.hip"),
     str(CSRC / "hashset.hip"),
+    str(CSRC / "event_rate.hip"),
     str(CSRC / "edit_distance.hip"),
 ]
 
