@@ -33,3 +33,6 @@ from .sklearn_detector import (
 
 __all__ += ["SklearnDetector", "SklearnDetectorConfig",
             "FrequencyDetector", "FrequencyDetectorConfig"]
+from .value_range import ValueRangeDetector, ValueRangeDetectorConfig
+
+__all__ += ["ValueRangeDetector", "ValueRangeDetectorConfig"]

@@ -48,6 +48,11 @@ class FusedPipelineDetectorConfig(CoreConfig):
     #: The line that completes a window alerts when an event's count in it
     #: is z_threshold sigmas off its EWMA baseline. None = off.
     event_rate: Optional[Dict[str, Any]] = None
+    #: numeric value ranges: [{kind, pos, event, name, slack, non_numeric,
+    #: min, max}], the first three as in watches. The field is read as a
+    #: decimal number; its smallest and largest value over the
+    #: data_use_training rows (or min / max) bound what is normal later.
+    ranges: List[Dict[str, Any]] = []
     device: Optional[str] = None
     seed: int = 1234
     #: capture the detect path as ONE hipGraph at this batch size (0 = off).
@@ -88,6 +93,7 @@ class FusedPipelineDetector(CoreComponent):
                 train_lines=cfg.data_use_training,
                 event_rate=(dict(cfg.event_rate)
                             if cfg.event_rate is not None else None),
+                ranges=[dict(r) for r in (cfg.ranges or [])],
                 seed=cfg.seed,
             ),
             device=self.device,
@@ -184,6 +190,8 @@ class FusedPipelineDetector(CoreComponent):
         combo = combo.cpu() if combo is not None else None
         rate_hits = out.get("rate_hits")
         rate_hits = rate_hits.cpu() if rate_hits is not None else None
+        range_code = out.get("range_code")
+        range_code = range_code.cpu() if range_code is not None else None
         now = int(time.time())
         alerts = []
         for i in idxs:
@@ -194,6 +202,8 @@ class FusedPipelineDetector(CoreComponent):
                 reasons.append("unknown combination")
             if rate_hits is not None and int(rate_hits[i]) > 0:
                 reasons.append(self._rate_reason(out, i))
+            if range_code is not None and bool(range_code[i].any()):
+                reasons.extend(self._range_reasons(out, range_code, i))
             if (self.pipe.model is not None
                     and float(scores[i]) > self.config.score_threshold):
                 what = ("embedding distance"
@@ -223,6 +233,25 @@ class FusedPipelineDetector(CoreComponent):
             who = "unparsed" if e == 0 else f"event {e}"
             parts.append(f"{who}: {int(counts[e])}/window (z={float(z[e]):+.1f})")
         return "event rate: " + "; ".join(parts)
+
+    def _range_reasons(self, out, range_code, i: int) -> List[str]:
+        """"value out of range: bytes = 18234511 above [0, 1048576]" or "not
+        a number: bytes" for every flagged range of row i. The bounds are
+        read from the device state here, when an alert is worded, and
+        nowhere on the hot path."""
+        state = self.pipe.value_ranges
+        lo, hi = state.lo.cpu(), state.hi.cpu()
+        reasons = []
+        for r in torch.nonzero(range_code[i], as_tuple=False).flatten().tolist():
+            code, name = int(range_code[i, r]), state.names[r]
+            if code == 3:
+                reasons.append(f"not a number: {name}")
+                continue
+            side = "below" if code == 1 else "above"
+            reasons.append(
+                f"value out of range: {name} = {float(out['range_value'][i, r]):.15g} "
+                f"{side} [{float(lo[r]):.15g}, {float(hi[r]):.15g}]")
+        return reasons
 
     def process_packed_frames(self, lines, lens, ids_blob, ids_off) -> List:
         """Engine packed-loop entry: tensors in (already decoded by the
@@ -323,11 +352,13 @@ class FusedPipelineDetector(CoreComponent):
         """COLLECTIVE merge of the data-parallel GPU hash sets (one
         batched insert-kernel call per peer table —
         parallel/dist.py::all_reduce_hashsets). Event-rate state is left
-        alone: each rank judges the rate of its own shard of the stream."""
+        alone: each rank judges the rate of its own shard of the stream.
+        Value ranges are merged: lo by MIN, hi by MAX, n by SUM."""
         import torch.distributed as tdist
 
         if not tdist.is_initialized() or tdist.get_world_size(group) <= 1:
             return
+        self._sync_value_ranges(group)
         if self.pipe.hashsets is None:
             return
         hs = self.pipe.hashsets
@@ -347,6 +378,21 @@ class FusedPipelineDetector(CoreComponent):
                 for w, values in enumerate(other):
                     hs.sets[w].update(values)
 
+    def _sync_value_ranges(self, group=None) -> None:
+        """COLLECTIVE: every rank ends with the smallest lo, the largest hi
+        and the summed n of all ranks, written into the tensors the kernels
+        (and a captured graph) read."""
+        import torch.distributed as tdist
+
+        state = self.pipe.value_ranges
+        if state is None:
+            return
+        lo, hi, n = state.lo.clone(), state.hi.clone(), state.n.clone()
+        tdist.all_reduce(lo, op=tdist.ReduceOp.MIN, group=group)
+        tdist.all_reduce(hi, op=tdist.ReduceOp.MAX, group=group)
+        tdist.all_reduce(n, op=tdist.ReduceOp.SUM, group=group)
+        state.merge_(lo, hi, n - state.n)  # n: the other ranks' share
+
     def state_dict(self) -> Dict[str, Any]:
         state: Dict[str, Any] = {"seen_lines": self.pipe.seen_lines}
         if self.pipe.hashsets is not None:
@@ -357,6 +403,8 @@ class FusedPipelineDetector(CoreComponent):
             state["embedding_stats"] = self.pipe.embedding_stats.state_dict()
         if self.pipe.event_rate is not None:
             state["event_rate"] = self.pipe.event_rate.state_dict()
+        if self.pipe.value_ranges is not None:
+            state["value_ranges"] = self.pipe.value_ranges.state_dict()
         return state
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
@@ -369,3 +417,5 @@ class FusedPipelineDetector(CoreComponent):
             self.pipe.embedding_stats.load_state_dict(state["embedding_stats"])
         if "event_rate" in state and self.pipe.event_rate is not None:
             self.pipe.event_rate.load_state_dict(state["event_rate"])
+        if "value_ranges" in state and self.pipe.value_ranges is not None:
+            self.pipe.value_ranges.load_state_dict(state["value_ranges"])

@@ -10,6 +10,7 @@ references).
 from __future__ import annotations
 
 import math
+import re
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -785,3 +786,228 @@ class EventRateState:
         for k in self._STATE:
             mine = getattr(self, k)
             mine.copy_(state[k].to(mine.dtype))
+
+
+# ---------------------------------------------------------------------------
+# detector: numeric value ranges (docs/kernels.md, "Value ranges" is the
+# definition; value_range.hip and value_range_step_cpu below implement it)
+# ---------------------------------------------------------------------------
+
+#: kernels.h limits of the grammar (tests compare them to the extension's)
+VR_MAX_SPAN = 17
+VR_MAX_DIGITS = 15
+
+_VR_NUMBER = re.compile(rb"[+-]?[0-9]+(\.[0-9]+)?")
+_RANGE_KEYS = ("kind", "pos", "event", "name", "slack", "non_numeric", "min", "max")
+
+
+def parse_number(span: bytes) -> Optional[float]:
+    """The value of ``span`` under the "Value ranges" grammar, or None when
+    it is not a number: the regular expression, the two length limits and
+    Python's correctly rounded ``float()``, with 0.0 in place of -0.0."""
+    if len(span) > VR_MAX_SPAN or _VR_NUMBER.fullmatch(span) is None:
+        return None
+    if sum(48 <= c <= 57 for c in span) > VR_MAX_DIGITS:
+        return None
+    v = float(span.decode("ascii"))
+    return 0.0 if v == 0.0 else v
+
+
+def range_spec_row(r: dict) -> List[int]:
+    """One range dict -> the kernel's spec row (kind, event, pos, flags):
+    a watch row whose pad word holds the flags, bit 0 = non_numeric alert."""
+    kind, event, pos, _ = watch_spec_row(r)
+    return [kind, event, pos, 1 if r.get("non_numeric", "ignore") == "alert" else 0]
+
+
+def range_name(r: dict) -> str:
+    """Alert name of a range: its ``name`` or ``variable <pos>`` /
+    ``header <pos>``."""
+    if r.get("name"):
+        return str(r["name"])
+    kind = "variable" if r.get("kind", "variable") == "variable" else "header"
+    return f"{kind} {int(r['pos'])}"
+
+
+def pack_ranges(specs: Sequence[dict]):
+    """List of range dicts -> (specs int32 [R, 4], slack f64 [R], lo f64
+    [R], hi f64 [R]) on the CPU: the host-side validation of everything the
+    kernels trust, and the start state (lo = +inf, hi = -inf, or the
+    configured min / max)."""
+    rows, slack, lo, hi = [], [], [], []
+    for i, r in enumerate(specs):
+        unknown = set(r) - set(_RANGE_KEYS)
+        if unknown:
+            raise ValueError(
+                f"range {i}: unknown key(s) {sorted(unknown)}; valid keys: "
+                f"{sorted(_RANGE_KEYS)}")
+        if "pos" not in r:
+            raise ValueError(f"range {i} has no 'pos': {dict(r)!r}")
+        if r.get("kind", "variable") not in ("variable", "header"):
+            raise ValueError(
+                f"range {i}: 'kind' must be 'variable' or 'header', got {r['kind']!r}")
+        if r.get("non_numeric", "ignore") not in ("ignore", "alert"):
+            raise ValueError(
+                f"range {i}: 'non_numeric' must be 'ignore' or 'alert', "
+                f"got {r['non_numeric']!r}")
+        row = range_spec_row(r)
+        if row[2] < 0:
+            raise ValueError(f"range {i}: 'pos' must be >= 0, got {row[2]}")
+        s = float(r.get("slack", 0.0))
+        if not (math.isfinite(s) and s >= 0.0):
+            raise ValueError(f"range {i}: 'slack' must be finite and >= 0, got {s}")
+        if ("min" in r) != ("max" in r):
+            raise ValueError(f"range {i}: 'min' and 'max' are given both or neither")
+        if "min" in r:
+            # + 0.0 turns -0.0 into 0.0, the only zero the parser yields
+            a, b = float(r["min"]) + 0.0, float(r["max"]) + 0.0
+            if not (math.isfinite(a) and math.isfinite(b)):
+                raise ValueError(f"range {i}: 'min' and 'max' must be finite, got {a}, {b}")
+            if a > b:
+                raise ValueError(f"range {i}: 'min' = {a} exceeds 'max' = {b}")
+        else:
+            a, b = math.inf, -math.inf
+        rows.append(row)
+        slack.append(s)
+        lo.append(a)
+        hi.append(b)
+    return (
+        torch.tensor(rows, dtype=torch.int32).reshape(-1, 4),
+        torch.tensor(slack, dtype=torch.float64),
+        torch.tensor(lo, dtype=torch.float64),
+        torch.tensor(hi, dtype=torch.float64),
+    )
+
+
+def value_range_step_cpu(lines, match: dict, specs, slack, lo, hi, n, train_upto: int):
+    """CPU mirror of ``_dmx_C.value_range_step``: lo, hi (f64 [R]) and n
+    (int64 [R]) are updated in place by the rows below train_upto, then
+    every (line, range) cell is judged against the updated state. Returns
+    (range_code int32 [B, R], range_value f64 [B, R]). Values come from
+    parse_number, the compares are Python floats: IEEE f64, one rounding
+    per operation."""
+    B, max_len = int(lines.shape[0]), int(lines.shape[1])
+    R = int(specs.shape[0])
+    if R < 1 or tuple(specs.shape) != (R, 4):
+        raise ValueError(f"specs must be int32 [R >= 1, 4], got {list(specs.shape)}")
+    for name, t in (("slack", slack), ("lo", lo), ("hi", hi), ("n", n)):
+        if tuple(t.shape) != (R,):
+            raise ValueError(f"{name} must hold R = {R} elements, got {list(t.shape)}")
+    if not 0 <= int(train_upto) <= B:
+        raise ValueError(f"train_upto must be within 0 .. B = {B}, got {train_upto}")
+    code = torch.zeros((B, R), dtype=torch.int32)
+    value = torch.zeros((B, R), dtype=torch.float64)
+    if B == 0:
+        return code, value
+    rows = [bytes(x) for x in lines.numpy()]
+    ev = match["event_id"].tolist()
+    caps, ncaps = match["caps"].tolist(), match["n_caps"].tolist()
+    fcaps, nfcaps = match["fmt_caps"].tolist(), match["n_fmt_caps"].tolist()
+    spec = specs.tolist()
+    sl = slack.tolist()
+
+    def field(i: int, r: int) -> Optional[bytes]:
+        """The span range r reads on line i; None when the range is not
+        relevant for the line or the field is absent."""
+        kind, event, pos, _ = spec[r]
+        start = end = -1
+        if pos >= 0:
+            if kind == 0:
+                if (event < 0 or ev[i] == event) and pos < min(ncaps[i], len(caps[i])):
+                    start, end = caps[i][pos]
+            elif pos < min(nfcaps[i], len(fcaps[i])):
+                start, end = fcaps[i][pos]
+        if start < 0 or end < start or end > max_len:
+            return None
+        return rows[i][start:end]
+
+    spans = [[field(i, r) for r in range(R)] for i in range(B)]
+    vals = [[None if s is None else parse_number(s) for s in row] for row in spans]
+    for r in range(R):
+        a, b, cnt = float(lo[r]), float(hi[r]), int(n[r])
+        for i in range(int(train_upto)):
+            v = vals[i][r]
+            if v is not None:
+                a, b, cnt = min(a, v), max(b, v), cnt + 1
+        lo[r], hi[r], n[r] = a, b, cnt
+        alert_nan = bool(spec[r][3] & 1)
+        for i in range(B):
+            v = vals[i][r]
+            if v is not None:
+                value[i, r] = v
+            if i < train_upto or spans[i][r] is None:
+                continue
+            if v is None:
+                code[i, r] = 3 if alert_nan else 0
+            elif a <= b:
+                w = b - a
+                m = sl[r] * w
+                if v < a - m:
+                    code[i, r] = 1
+                elif v > b + m:
+                    code[i, r] = 2
+    return code, value
+
+
+def value_range_step(lines, match: dict, specs, slack, lo, hi, n, train_upto: int):
+    """One batch of the value-range stage on lines' device."""
+    if lines.is_cuda:
+        code, value = _require_ext().value_range_step(
+            lines, match["event_id"], match["caps"], match["n_caps"],
+            match["fmt_caps"], match["n_fmt_caps"], specs, slack, lo, hi, n,
+            int(train_upto))
+        return code, value
+    return value_range_step_cpu(lines, match, specs, slack, lo, hi, n, int(train_upto))
+
+
+class ValueRangeState:
+    """The value-range stage's tensors on ``device``: the packed specs and
+    ``slack`` (constant) and the learned ``lo``, ``hi`` (f64 [R]) and ``n``
+    (int64 [R]). ``step`` fits and judges one batch without a host read, so
+    it can be captured into a hipGraph; ``load_state_dict`` and ``merge_``
+    write into the same tensors, which a captured graph keeps reading."""
+
+    _STATE = ("lo", "hi", "n")
+
+    def __init__(self, specs: Sequence[dict], device="cpu") -> None:
+        if len(specs) == 0:
+            raise ValueError("ValueRangeState needs at least one range")
+        rows, slack, lo, hi = pack_ranges(specs)
+        self.R = int(rows.shape[0])
+        self.names = [range_name(r) for r in specs]
+        self.device = torch.device(device)
+        self.specs = rows.to(self.device)
+        self.slack = slack.to(self.device)
+        self.lo = lo.to(self.device)
+        self.hi = hi.to(self.device)
+        self.n = torch.zeros(self.R, dtype=torch.int64, device=self.device)
+
+    def step(self, lines: torch.Tensor, match: dict, train_upto: int = 0):
+        """(range_code int32 [B, R], range_value f64 [B, R]) of one parsed
+        batch; rows below train_upto move lo, hi and n first."""
+        return value_range_step(lines, match, self.specs, self.slack, self.lo,
+                                self.hi, self.n, train_upto)
+
+    def state_dict(self) -> dict:
+        return {k: getattr(self, k).detach().cpu().clone() for k in self._STATE}
+
+    def load_state_dict(self, state: dict) -> None:
+        for k in self._STATE:
+            if tuple(state[k].shape) != (self.R,):
+                raise ValueError(
+                    f"value-range checkpoint holds {k} {list(state[k].shape)} but "
+                    f"this instance is configured for R = {self.R} ranges")
+        for k in self._STATE:
+            mine = getattr(self, k)
+            mine.copy_(state[k].to(mine.dtype))
+
+    def merge_(self, lo: torch.Tensor, hi: torch.Tensor, n: torch.Tensor) -> None:
+        """Fold another state of the same ranges into this one, in place:
+        lo = min, hi = max, n = sum."""
+        for name, t in (("lo", lo), ("hi", hi), ("n", n)):
+            if tuple(t.shape) != (self.R,):
+                raise ValueError(
+                    f"merge_: {name} must hold R = {self.R} elements, got {list(t.shape)}")
+        self.lo.copy_(torch.minimum(self.lo, lo.to(self.lo)))
+        self.hi.copy_(torch.maximum(self.hi, hi.to(self.hi)))
+        self.n.add_(n.to(self.n))

@@ -725,6 +725,78 @@ std::vector<torch::Tensor> event_rate_step(
   return {rate_counts, rate_z, rate_hits, rate_slot};
 }
 
+// ---- value ranges (docs/kernels.md, "Value ranges") ---------------------------
+
+py::dict value_range_limits() {
+  py::dict d;
+  d["max_span"] = VR_MAX_SPAN;
+  d["max_digits"] = VR_MAX_DIGITS;
+  return d;
+}
+
+// One batch of the value-range stage. lo, hi and n are updated in place by
+// the rows below train_upto; returns (range_code int32 [B, R], range_value
+// f64 [B, R]). Nothing here reads a tensor's values.
+std::vector<torch::Tensor> value_range_step(
+    torch::Tensor lines, torch::Tensor event_id, torch::Tensor caps,
+    torch::Tensor n_caps, torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
+    torch::Tensor specs, torch::Tensor slack, torch::Tensor lo,
+    torch::Tensor hi, torch::Tensor n, int64_t train_upto) {
+  check_arg(lines, "lines", torch::kUInt8, 2);
+  const auto B = lines.size(0), max_len = lines.size(1);
+  check_arg(event_id, "event_id", torch::kInt32, 1);
+  check_numel(event_id, "event_id", B, "B");
+  check_caps(caps, "caps", B);
+  check_arg(n_caps, "n_caps", torch::kInt32, 1);
+  check_numel(n_caps, "n_caps", B, "B");
+  check_caps(fmt_caps, "fmt_caps", B);
+  check_arg(n_fmt_caps, "n_fmt_caps", torch::kInt32, 1);
+  check_numel(n_fmt_caps, "n_fmt_caps", B, "B");
+  check_specs(specs, "specs", "R");
+  const auto R = specs.size(0);
+  TORCH_CHECK(R >= 1, "specs must hold at least one range, got ",
+              specs.sizes());
+  check_arg(slack, "slack", torch::kFloat64, 1);
+  check_numel(slack, "slack", R, "R");
+  check_arg(lo, "lo", torch::kFloat64, 1);
+  check_numel(lo, "lo", R, "R");
+  check_arg(hi, "hi", torch::kFloat64, 1);
+  check_numel(hi, "hi", R, "R");
+  check_arg(n, "n", torch::kInt64, 1);
+  check_numel(n, "n", R, "R");
+  TORCH_CHECK(train_upto >= 0 && train_upto <= B,
+              "train_upto must be within 0 .. B = ", B, ", got ", train_upto);
+  TORCH_CHECK(B * R < (int64_t(1) << 31), "lines: B * R = ", B, " * ", R,
+              " must be below 2^31 (the kernel's flat index)");
+  DeviceScope dev({{"lines", lines},
+                   {"event_id", event_id},
+                   {"caps", caps},
+                   {"n_caps", n_caps},
+                   {"fmt_caps", fmt_caps},
+                   {"n_fmt_caps", n_fmt_caps},
+                   {"specs", specs},
+                   {"slack", slack},
+                   {"lo", lo},
+                   {"hi", hi},
+                   {"n", n}});
+  // every element of both outputs is written by the judge kernel
+  auto range_code = torch::empty({B, R}, event_id.options());
+  auto range_value =
+      torch::empty({B, R}, event_id.options().dtype(torch::kFloat64));
+  if (B == 0) return {range_code, range_value};
+  dmx_launch_value_range(
+      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
+      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
+      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
+      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)R,
+      slack.data_ptr<double>(), lo.data_ptr<double>(), hi.data_ptr<double>(),
+      n.data_ptr<int64_t>(), (int)B, (int)train_upto,
+      range_code.data_ptr<int32_t>(), range_value.data_ptr<double>(),
+      dev.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {range_code, range_value};
+}
+
 }  // namespace
 
 void register_codec(py::module_& m);   // codec.cpp
@@ -767,6 +839,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "event-rate windows: count one batch, roll the complete windows");
   m.def("event_rate_limits", &event_rate_limits,
         "limits of event_rate_step (max_events, max_cells)");
+  m.def("value_range_step", &value_range_step,
+        "value ranges: fit the training rows, judge every (line, range)");
+  m.def("value_range_limits", &value_range_limits,
+        "limits of the value-range grammar (max_span, max_digits)");
   m.def("edit_distance", &edit_distance,
         "batched Levenshtein distances (wavefront DP in LDS)");
 }

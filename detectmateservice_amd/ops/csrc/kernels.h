@@ -30,6 +30,8 @@ constexpr int TM_MAX_LINE = 512;      // template_match: bytes per line
 constexpr int LDS_DEFAULT_LIMIT = 64 * 1024;  // dynamic LDS without opt-in
 constexpr int ER_MAX_EVENTS = 8192;   // event_rate: bins (32 KiB LDS histogram)
 constexpr int64_t ER_MAX_CELLS = int64_t(1) << 24;  // event_rate: NW * E
+constexpr int VR_MAX_SPAN = 17;       // value_range: bytes of a number
+constexpr int VR_MAX_DIGITS = 15;     // value_range: digits (10^15 < 2^53)
 
 // Dynamic LDS of dmx_template_match: the segment blob (16-B rounded) plus
 // one staged line per wave. The kernel carves its arena the same way.
@@ -204,6 +206,22 @@ void dmx_launch_event_rate(const int32_t* event_id, const int32_t* n_valid,
                            double* base, int32_t* rate_counts, double* rate_z,
                            int32_t* rate_hits, int32_t* rate_slot,
                            hipStream_t stream);
+
+// value_range.hip: one batch of the value-range stage (the fit launch only
+// when train_upto > 0, then the judge launch). specs: [R, 4] int32 rows laid
+// out like the watch specs, the pad word holding flags (bit 0 = a field that
+// is not a number alerts). slack f64 [R], read only. State, updated in
+// place: lo, hi f64 [R]; n int64 [R]. Outputs, fully written: range_code
+// int32 [B, R], range_value f64 [B, R].
+void dmx_launch_value_range(const uint8_t* lines, int max_len,
+                            const int32_t* event_id, const int32_t* caps,
+                            const int32_t* n_caps, int max_caps,
+                            const int32_t* fmt_caps,
+                            const int32_t* n_fmt_caps, int max_fmt_caps,
+                            const int32_t* specs, int R, const double* slack,
+                            double* lo, double* hi, int64_t* n, int B,
+                            int train_upto, int32_t* range_code,
+                            double* range_value, hipStream_t stream);
 
 // edit_distance.hip
 void dmx_launch_edit_distance(const uint8_t* A, const int32_t* a_len, int Na,

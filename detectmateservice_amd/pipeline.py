@@ -21,8 +21,13 @@ Stage structure per batch (all on `device`):
      "Event-rate windows"). The only stage whose verdict is about the stream
      and not about one line: its state lives on the device and the line that
      completes a window carries the alert.
+  5. With ``ranges`` configured: each range's field is parsed as a decimal
+     number from the line bytes and judged against the smallest and largest
+     value seen in training (docs/kernels.md, "Value ranges"); one launch in
+     the steady state, state on the device.
 Anomaly = NewValue unseen-value hit OR unseen combination OR transformer
-score > threshold OR, on a window's boundary line, a flagged event rate.
+score > threshold OR, on a window's boundary line, a flagged event rate OR a
+numeric field outside its learned range.
 
 ``score_mode`` says what the transformer score is. ``"head"`` (default) is
 the model's linear score head. ``"embedding"`` is the distance of the line's
@@ -74,6 +79,12 @@ class PipelineConfig:
     #: window_lines 1000, ewma_alpha 0.3, z_threshold 4.0, min_windows 3);
     #: None = stage off, {} = on with the defaults
     event_rate: Optional[dict] = None
+    #: numeric value ranges: list of dicts written like `watches` entries
+    #: plus the optional keys name, slack, non_numeric ("ignore" | "alert")
+    #: and min / max (docs/kernels.md, "Value ranges"). The smallest and
+    #: largest value of the field over the first train_lines rows are kept
+    #: on the device; a later value outside them alerts.
+    ranges: Sequence[dict] = ()
     bert: BertTinyConfig = field(default_factory=BertTinyConfig)
     seed: int = 1234
 
@@ -139,6 +150,10 @@ class GpuPipeline:
             self.event_rate = ops.EventRateState(
                 len(self.matcher.templates), device=self.device,
                 **{**ops.EVENT_RATE_DEFAULTS, **config.event_rate})
+        self.value_ranges: Optional[ops.ValueRangeState] = (
+            ops.ValueRangeState(list(config.ranges), device=self.device)
+            if len(config.ranges) else None
+        )
         self.seen_lines = 0
         # hipGraph capture state (enable_graph(); steady-state detect only)
         self._graph = None
@@ -157,6 +172,9 @@ class GpuPipeline:
         combo_unseen [B, C] (None without combos) and, with event_rate
         configured, rate_hits [B], rate_slot [B], rate_counts [NW, E] and
         rate_z [NW, E] (absent otherwise: ``out.get("rate_hits")`` is None).
+        With ranges configured (and only then) range_code int32 [B, R] (0 =
+        nothing, 1 = below, 2 = above, 3 = not a number) and range_value f64
+        [B, R].
 
         ``n_valid`` and ``rate`` concern the event-rate stage alone, the one
         stage with stream state: only the first n_valid rows (default: all)
@@ -173,6 +191,7 @@ class GpuPipeline:
                 "match": None,
                 **(dict.fromkeys(self._RATE_KEYS)
                    if self.event_rate is not None else {}),
+                **self._empty_range_out(lines.device),
             }
         # roctx-visible stage ranges (torch.cuda.nvtx maps to rocTracer
         # markers on ROCm — SURVEY.md §5.1 tracing requirement)
@@ -196,6 +215,18 @@ class GpuPipeline:
             if _rng:
                 torch.cuda.nvtx.range_push("dmx::event_rate")
             rate_out = self.event_rate.step(match["event_id"], n_valid, train_upto)
+            if _rng:
+                torch.cuda.nvtx.range_pop()
+
+        # value ranges: rows below train_upto move lo / hi / n, every row is
+        # judged against the state after them; the two keys exist only with
+        # ranges configured
+        range_out: Dict[str, torch.Tensor] = {}
+        if self.value_ranges is not None:
+            if _rng:
+                torch.cuda.nvtx.range_push("dmx::value_range")
+            code, value = self.value_ranges.step(lines, match, train_upto)
+            range_out = {"range_code": code, "range_value": value}
             if _rng:
                 torch.cuda.nvtx.range_pop()
 
@@ -257,6 +288,8 @@ class GpuPipeline:
         if rate_out.get("rate_hits") is not None:
             # non-zero only on a boundary line outside the training phase
             anomaly = anomaly | (rate_out["rate_hits"] > 0)
+        if range_out:
+            anomaly = anomaly | (range_out["range_code"] != 0).any(dim=1)
         return {
             "event_id": match["event_id"],
             "anomaly": anomaly,
@@ -265,6 +298,17 @@ class GpuPipeline:
             "combo_unseen": combo_unseen,
             "match": match,
             **rate_out,
+            **range_out,
+        }
+
+    def _empty_range_out(self, device) -> Dict[str, torch.Tensor]:
+        """The value-range keys of an empty batch ({} without ranges)."""
+        if self.value_ranges is None:
+            return {}
+        R = self.value_ranges.R
+        return {
+            "range_code": torch.zeros((0, R), dtype=torch.int32, device=device),
+            "range_value": torch.zeros((0, R), dtype=torch.float64, device=device),
         }
 
     def _embedding_scores(

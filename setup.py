@@ -29,6 +29,7 @@ sources = [
     str(CSRC / "template_match.hip"),
     str(CSRC / "hashset.hip"),
     str(CSRC / "event_rate.hip"),
+    str(CSRC / "value_range.hip"),
     str(CSRC / "edit_distance.hip"),
 ]
 
