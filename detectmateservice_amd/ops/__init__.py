@@ -372,7 +372,6 @@ class GpuHashSets:
 
     def state_dict(self):
         if self.device.type == "cuda":
-            nz = self.tables[self.tables != 0]
             return {"type": "gpu", "tables": self.tables.cpu()}
         return {"type": "cpu", "sets": [sorted(s) for s in self.sets]}
 
@@ -422,6 +421,34 @@ def fnv1a64(data: bytes, lower: bool = False) -> int:
     return h | 1
 
 
+def _parsed_args(lines, match: dict):
+    """The parsed batch as the extension's field entry points take it: six
+    positional tensors (docs/kernels.md, "Parsed batch and field span")."""
+    return (lines, match["event_id"], match["caps"], match["n_caps"],
+            match["fmt_caps"], match["n_fmt_caps"])
+
+
+def _field_span(parsed, max_len: int, spec, i: int) -> Optional[Tuple[int, int]]:
+    """CPU mirror of field_span (field_span.h): (start, end) of the field
+    that the spec row (kind, event, pos, _) names on line i, or None when the
+    spec is not relevant for the line or the field is absent. ``parsed`` is
+    _parsed_args without the lines, each tensor as nested lists."""
+    event_id, caps, n_caps, fmt_caps, n_fmt_caps = parsed
+    kind, event, pos = spec[0], spec[1], spec[2]
+    if not (kind != 0 or event < 0 or event_id[i] == event) or pos < 0:
+        return None
+    if kind != 0:
+        table, there = fmt_caps[i], pos < min(n_fmt_caps[i], len(fmt_caps[i]))
+    else:
+        table, there = caps[i], pos < min(n_caps[i], len(caps[i]))
+    if not there:
+        return None
+    start, end = table[pos]
+    if start < 0 or end < start or end > max_len:
+        return None
+    return start, end
+
+
 def watch_hashes_cpu(
     lines: torch.Tensor,
     match: dict,
@@ -429,35 +456,23 @@ def watch_hashes_cpu(
     lower: bool = False,
 ) -> torch.Tensor:
     """CPU mirror of dmx_watch_hashes."""
-    B = lines.shape[0]
+    B, max_len = int(lines.shape[0]), int(lines.shape[1])
     W = specs.shape[0]
     out = torch.zeros((B, W), dtype=torch.int64)
-    ev = match["event_id"]
-    caps, ncaps = match["caps"], match["n_caps"]
-    fcaps, nfcaps = match["fmt_caps"], match["n_fmt_caps"]
+    parsed = [t.tolist() for t in _parsed_args(lines, match)[1:]]
+    spec = specs.tolist()
     for i in range(B):
         row = bytes(lines[i].numpy().tobytes())
         for w in range(W):
-            kind, event, pos = int(specs[w, 0]), int(specs[w, 1]), int(specs[w, 2])
-            start = end = -1
-            if kind == 0:
-                if (event < 0 or int(ev[i]) == event) and pos < int(ncaps[i]):
-                    start, end = int(caps[i, pos, 0]), int(caps[i, pos, 1])
-            else:
-                if pos < int(nfcaps[i]):
-                    start, end = int(fcaps[i, pos, 0]), int(fcaps[i, pos, 1])
-            if start >= 0 and end >= start:
-                h = fnv1a64(row[start:end], lower)
-                out[i, w] = h - (1 << 64) if h >= (1 << 63) else h
+            span = _field_span(parsed, max_len, spec[w], i)
+            if span is not None:
+                out[i, w] = _as_i64(fnv1a64(row[span[0]:span[1]], lower))
     return out
 
 
 def watch_hashes(lines, match: dict, specs: torch.Tensor, lower: bool = False) -> torch.Tensor:
     if lines.is_cuda:
-        return _require_ext().watch_hashes(
-            lines, match["event_id"], match["caps"], match["n_caps"],
-            match["fmt_caps"], match["n_fmt_caps"], specs, lower,
-        )
+        return _require_ext().watch_hashes(*_parsed_args(lines, match), specs, lower)
     return watch_hashes_cpu(lines, match, specs, lower)
 
 
@@ -478,7 +493,7 @@ def _as_i64(h: int) -> int:
 
 
 def watch_spec_row(w: dict) -> List[int]:
-    """One watch dict -> the kernel's WatchSpec row (kind, event, pos, pad)."""
+    """One watch dict -> the kernel's FieldSpec row (kind, event, pos, pad)."""
     kind = 0 if w.get("kind", "variable") == "variable" else 1
     return [kind, int(w.get("event", -1)), int(w["pos"]), 0]
 
@@ -577,10 +592,7 @@ def watch_combo_hashes(
     """Watch hashes and combination hashes of a parsed batch, [B, W + C]."""
     if lines.is_cuda:
         return _require_ext().watch_combo_hashes(
-            lines, match["event_id"], match["caps"], match["n_caps"],
-            match["fmt_caps"], match["n_fmt_caps"], specs, members, combo_off,
-            lower,
-        )
+            *_parsed_args(lines, match), specs, members, combo_off, lower)
     return watch_combo_hashes_cpu(lines, match, specs, members, combo_off, lower)
 
 
@@ -900,28 +912,17 @@ def value_range_step_cpu(lines, match: dict, specs, slack, lo, hi, n, train_upto
     if B == 0:
         return code, value
     rows = [bytes(x) for x in lines.numpy()]
-    ev = match["event_id"].tolist()
-    caps, ncaps = match["caps"].tolist(), match["n_caps"].tolist()
-    fcaps, nfcaps = match["fmt_caps"].tolist(), match["n_fmt_caps"].tolist()
+    parsed = [t.tolist() for t in _parsed_args(lines, match)[1:]]
     spec = specs.tolist()
     sl = slack.tolist()
-
-    def field(i: int, r: int) -> Optional[bytes]:
-        """The span range r reads on line i; None when the range is not
-        relevant for the line or the field is absent."""
-        kind, event, pos, _ = spec[r]
-        start = end = -1
-        if pos >= 0:
-            if kind == 0:
-                if (event < 0 or ev[i] == event) and pos < min(ncaps[i], len(caps[i])):
-                    start, end = caps[i][pos]
-            elif pos < min(nfcaps[i], len(fcaps[i])):
-                start, end = fcaps[i][pos]
-        if start < 0 or end < start or end > max_len:
-            return None
-        return rows[i][start:end]
-
-    spans = [[field(i, r) for r in range(R)] for i in range(B)]
+    # the bytes range r reads on line i; None when the range is not relevant
+    # for the line or the field is absent
+    spans = [[None for _ in range(R)] for _ in range(B)]
+    for i in range(B):
+        for r in range(R):
+            span = _field_span(parsed, max_len, spec[r], i)
+            if span is not None:
+                spans[i][r] = rows[i][span[0]:span[1]]
     vals = [[None if s is None else parse_number(s) for s in row] for row in spans]
     for r in range(R):
         a, b, cnt = float(lo[r]), float(hi[r]), int(n[r])
@@ -953,9 +954,7 @@ def value_range_step(lines, match: dict, specs, slack, lo, hi, n, train_upto: in
     """One batch of the value-range stage on lines' device."""
     if lines.is_cuda:
         code, value = _require_ext().value_range_step(
-            lines, match["event_id"], match["caps"], match["n_caps"],
-            match["fmt_caps"], match["n_fmt_caps"], specs, slack, lo, hi, n,
-            int(train_upto))
+            *_parsed_args(lines, match), specs, slack, lo, hi, n, int(train_upto))
         return code, value
     return value_range_step_cpu(lines, match, specs, slack, lo, hi, n, int(train_upto))
 

@@ -64,14 +64,17 @@ struct Arg {
 // the tensors' device rather than to whatever device the caller left set.
 class DeviceScope {
  public:
-  DeviceScope(std::initializer_list<Arg> args) {
+  // `more` continues `args` (parsed_batch_scope puts its own list first)
+  DeviceScope(std::initializer_list<Arg> args,
+              std::initializer_list<Arg> more = {}) {
     const Arg& first = *args.begin();
     TORCH_CHECK(first.t.is_cuda(), first.name, " must be on a GPU, got ",
                 first.t.device());
-    for (const Arg& a : args)
-      TORCH_CHECK(a.t.device() == first.t.device(), a.name, " must be on ",
-                  first.name, "'s device ", first.t.device(), ", got ",
-                  a.t.device());
+    for (const auto& list : {args, more})
+      for (const Arg& a : list)
+        TORCH_CHECK(a.t.device() == first.t.device(), a.name, " must be on ",
+                    first.name, "'s device ", first.t.device(), ", got ",
+                    a.t.device());
     guard_.set_device(first.t.device());
     stream_ = at::hip::getCurrentHIPStream().stream();
   }
@@ -505,13 +508,14 @@ void check_specs(const torch::Tensor& t, const char* name, const char* rows) {
               ", 4] (kind, event, pos, pad), got ", t.sizes());
 }
 
-// The parsed batch that both watch-hash entry points read.
-void check_watch_args(const torch::Tensor& lines,
-                      const torch::Tensor& event_id, const torch::Tensor& caps,
-                      const torch::Tensor& n_caps,
-                      const torch::Tensor& fmt_caps,
-                      const torch::Tensor& n_fmt_caps,
-                      const torch::Tensor& specs) {
+// The matcher's six tensors, as every field binding takes them: checked
+// in this order, then viewed as the launchers' ParsedBatch.
+ParsedBatch check_parsed_batch(const torch::Tensor& lines,
+                               const torch::Tensor& event_id,
+                               const torch::Tensor& caps,
+                               const torch::Tensor& n_caps,
+                               const torch::Tensor& fmt_caps,
+                               const torch::Tensor& n_fmt_caps) {
   check_arg(lines, "lines", torch::kUInt8, 2);
   const auto B = lines.size(0);
   check_arg(event_id, "event_id", torch::kInt32, 1);
@@ -522,31 +526,45 @@ void check_watch_args(const torch::Tensor& lines,
   check_caps(fmt_caps, "fmt_caps", B);
   check_arg(n_fmt_caps, "n_fmt_caps", torch::kInt32, 1);
   check_numel(n_fmt_caps, "n_fmt_caps", B, "B");
-  check_specs(specs, "specs", "W");
+  return {lines.data_ptr<uint8_t>(),     event_id.data_ptr<int32_t>(),
+          caps.data_ptr<int32_t>(),      n_caps.data_ptr<int32_t>(),
+          fmt_caps.data_ptr<int32_t>(),  n_fmt_caps.data_ptr<int32_t>(),
+          (int)B,                        (int)lines.size(1),
+          (int)caps.size(1),             (int)fmt_caps.size(1)};
+}
+
+// Device clause of the same six tensors, then of the binding's own (`more`).
+DeviceScope parsed_batch_scope(const torch::Tensor& lines,
+                               const torch::Tensor& event_id,
+                               const torch::Tensor& caps,
+                               const torch::Tensor& n_caps,
+                               const torch::Tensor& fmt_caps,
+                               const torch::Tensor& n_fmt_caps,
+                               std::initializer_list<Arg> more) {
+  return DeviceScope({{"lines", lines},
+                      {"event_id", event_id},
+                      {"caps", caps},
+                      {"n_caps", n_caps},
+                      {"fmt_caps", fmt_caps},
+                      {"n_fmt_caps", n_fmt_caps}},
+                     more);
 }
 
 torch::Tensor watch_hashes(torch::Tensor lines, torch::Tensor event_id,
                            torch::Tensor caps, torch::Tensor n_caps,
                            torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
                            torch::Tensor specs, bool lower) {
-  check_watch_args(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps, specs);
-  const auto B = lines.size(0), max_len = lines.size(1);
-  const auto W = specs.size(0);
-  DeviceScope dev({{"lines", lines},
-                   {"event_id", event_id},
-                   {"caps", caps},
-                   {"n_caps", n_caps},
-                   {"fmt_caps", fmt_caps},
-                   {"n_fmt_caps", n_fmt_caps},
-                   {"specs", specs}});
+  const ParsedBatch batch =
+      check_parsed_batch(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps);
+  check_specs(specs, "specs", "W");
+  const auto B = lines.size(0), W = specs.size(0);
+  DeviceScope dev = parsed_batch_scope(lines, event_id, caps, n_caps, fmt_caps,
+                                       n_fmt_caps, {{"specs", specs}});
   auto hashes = torch::zeros({B, W}, lines.options().dtype(torch::kInt64));
   if (B == 0 || W == 0) return hashes;
-  dmx_launch_watch_hashes(
-      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
-      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
-      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
-      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)W, (int)B,
-      lower ? 1 : 0, hashes.data_ptr<int64_t>(), dev.stream());
+  dmx_launch_watch_hashes(batch, specs.data_ptr<int32_t>(), (int)W,
+                          lower ? 1 : 0, hashes.data_ptr<int64_t>(),
+                          dev.stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return hashes;
 }
@@ -563,9 +581,10 @@ torch::Tensor watch_combo_hashes(torch::Tensor lines, torch::Tensor event_id,
                                  torch::Tensor n_fmt_caps, torch::Tensor specs,
                                  torch::Tensor members,
                                  torch::Tensor combo_off, bool lower) {
-  check_watch_args(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps, specs);
-  const auto B = lines.size(0), max_len = lines.size(1);
-  const auto W = specs.size(0);
+  const ParsedBatch batch =
+      check_parsed_batch(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps);
+  check_specs(specs, "specs", "W");
+  const auto B = lines.size(0), W = specs.size(0);
   check_specs(members, "members", "M");
   const auto M = members.size(0);
   check_arg(combo_off, "combo_off", torch::kInt32, 1);
@@ -586,24 +605,15 @@ torch::Tensor watch_combo_hashes(torch::Tensor lines, torch::Tensor event_id,
   }
   TORCH_CHECK(B * (W + C) < (int64_t(1) << 31), "lines: B * (W + C) = ", B,
               " * ", W + C, " must be below 2^31 (the kernel's flat index)");
-  DeviceScope dev({{"lines", lines},
-                   {"event_id", event_id},
-                   {"caps", caps},
-                   {"n_caps", n_caps},
-                   {"fmt_caps", fmt_caps},
-                   {"n_fmt_caps", n_fmt_caps},
-                   {"specs", specs},
-                   {"members", members},
-                   {"combo_off", combo_off}});
+  DeviceScope dev = parsed_batch_scope(
+      lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps,
+      {{"specs", specs}, {"members", members}, {"combo_off", combo_off}});
   auto hashes = torch::zeros({B, W + C}, lines.options().dtype(torch::kInt64));
   if (B == 0 || W + C == 0) return hashes;
   dmx_launch_watch_combo_hashes(
-      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
-      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
-      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
-      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)W,
-      members.data_ptr<int32_t>(), (int)M, combo_off.data_ptr<int32_t>(),
-      (int)C, (int)B, lower ? 1 : 0, hashes.data_ptr<int64_t>(), dev.stream());
+      batch, specs.data_ptr<int32_t>(), (int)W, members.data_ptr<int32_t>(),
+      (int)M, combo_off.data_ptr<int32_t>(), (int)C, lower ? 1 : 0,
+      hashes.data_ptr<int64_t>(), dev.stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return hashes;
 }
@@ -742,18 +752,10 @@ std::vector<torch::Tensor> value_range_step(
     torch::Tensor n_caps, torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
     torch::Tensor specs, torch::Tensor slack, torch::Tensor lo,
     torch::Tensor hi, torch::Tensor n, int64_t train_upto) {
-  check_arg(lines, "lines", torch::kUInt8, 2);
-  const auto B = lines.size(0), max_len = lines.size(1);
-  check_arg(event_id, "event_id", torch::kInt32, 1);
-  check_numel(event_id, "event_id", B, "B");
-  check_caps(caps, "caps", B);
-  check_arg(n_caps, "n_caps", torch::kInt32, 1);
-  check_numel(n_caps, "n_caps", B, "B");
-  check_caps(fmt_caps, "fmt_caps", B);
-  check_arg(n_fmt_caps, "n_fmt_caps", torch::kInt32, 1);
-  check_numel(n_fmt_caps, "n_fmt_caps", B, "B");
+  const ParsedBatch batch =
+      check_parsed_batch(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps);
   check_specs(specs, "specs", "R");
-  const auto R = specs.size(0);
+  const auto B = lines.size(0), R = specs.size(0);
   TORCH_CHECK(R >= 1, "specs must hold at least one range, got ",
               specs.sizes());
   check_arg(slack, "slack", torch::kFloat64, 1);
@@ -768,31 +770,19 @@ std::vector<torch::Tensor> value_range_step(
               "train_upto must be within 0 .. B = ", B, ", got ", train_upto);
   TORCH_CHECK(B * R < (int64_t(1) << 31), "lines: B * R = ", B, " * ", R,
               " must be below 2^31 (the kernel's flat index)");
-  DeviceScope dev({{"lines", lines},
-                   {"event_id", event_id},
-                   {"caps", caps},
-                   {"n_caps", n_caps},
-                   {"fmt_caps", fmt_caps},
-                   {"n_fmt_caps", n_fmt_caps},
-                   {"specs", specs},
-                   {"slack", slack},
-                   {"lo", lo},
-                   {"hi", hi},
-                   {"n", n}});
+  DeviceScope dev = parsed_batch_scope(
+      lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps,
+      {{"specs", specs}, {"slack", slack}, {"lo", lo}, {"hi", hi}, {"n", n}});
   // every element of both outputs is written by the judge kernel
   auto range_code = torch::empty({B, R}, event_id.options());
   auto range_value =
       torch::empty({B, R}, event_id.options().dtype(torch::kFloat64));
   if (B == 0) return {range_code, range_value};
   dmx_launch_value_range(
-      lines.data_ptr<uint8_t>(), (int)max_len, event_id.data_ptr<int32_t>(),
-      caps.data_ptr<int32_t>(), n_caps.data_ptr<int32_t>(), (int)caps.size(1),
-      fmt_caps.data_ptr<int32_t>(), n_fmt_caps.data_ptr<int32_t>(),
-      (int)fmt_caps.size(1), specs.data_ptr<int32_t>(), (int)R,
-      slack.data_ptr<double>(), lo.data_ptr<double>(), hi.data_ptr<double>(),
-      n.data_ptr<int64_t>(), (int)B, (int)train_upto,
-      range_code.data_ptr<int32_t>(), range_value.data_ptr<double>(),
-      dev.stream());
+      batch, specs.data_ptr<int32_t>(), (int)R, slack.data_ptr<double>(),
+      lo.data_ptr<double>(), hi.data_ptr<double>(), n.data_ptr<int64_t>(),
+      (int)train_upto, range_code.data_ptr<int32_t>(),
+      range_value.data_ptr<double>(), dev.stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {range_code, range_value};
 }

@@ -10,6 +10,7 @@
 // Tables: [W, capacity] u64, 0 = empty (hashes are forced odd). Linear
 // probing; capacity is a power of two sized >= 4x expected cardinality.
 #include "common.h"
+#include "field_span.h"
 #include "kernels.h"
 
 #define EMPTY_KEY 0ull
@@ -26,88 +27,24 @@ static __device__ __forceinline__ unsigned long long fnv1a64(
   return h | 1ull;  // never EMPTY_KEY
 }
 
-// Watch spec (mirrors library/detectors/new_value.py::_WatchSpec):
-//   kind 0 = content variable: capture index `pos` of lines whose
-//            event_id == event (event < 0 -> any event)  [caps table]
-//   kind 1 = header variable: format capture index `pos`  [fmt_caps table]
-struct WatchSpec {
-  int kind;
-  int event;
-  int pos;
-  int _pad;
-};
+// Hash of the span that spec `s` watches on `line`: 0 when the spec is not
+// relevant for the line or the field is absent (field_span.h).
+static __device__ __forceinline__ unsigned long long field_hash(
+    const ParsedBatch& batch, const FieldSpec s, int line, int lower) {
+  const FieldSpan f = field_span(batch, s, line);
+  if (f.len < 0) return 0ull;
+  return fnv1a64(batch.lines + (long)line * batch.max_len + f.start, f.len,
+                 lower);
+}
 
-// For each (line, watch): compute the hash of the watched span (0 if the
-// field is absent for that line).
+// For each (line, watch): the hash of the watched span.
 extern "C" __global__ __launch_bounds__(256)
 void dmx_watch_hashes(
-    const unsigned char* __restrict__ lines, int max_len,
-    const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps,
-    const WatchSpec* __restrict__ specs, int W,
-    int B, int lower,
-    unsigned long long* __restrict__ hashes) {  // [B, W]
+    const ParsedBatch batch, const FieldSpec* __restrict__ specs, int W,
+    int lower, unsigned long long* __restrict__ hashes) {  // [B, W]
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)B * W) return;
-  const int line = idx / W;
-  const int w = idx % W;
-  const WatchSpec s = specs[w];
-  unsigned long long h = 0ull;
-
-  int start = -1, end = -1;
-  if (s.kind == 0) {
-    if ((s.event < 0 || event_id[line] == s.event) && s.pos < n_caps[line]) {
-      start = caps[((long)line * max_caps + s.pos) * 2];
-      end = caps[((long)line * max_caps + s.pos) * 2 + 1];
-    }
-  } else {
-    if (n_fmt_caps && s.pos < n_fmt_caps[line]) {
-      start = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2];
-      end = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2 + 1];
-    }
-  }
-  if (start >= 0 && end >= start)
-    h = fnv1a64(lines + (long)line * max_len + start, end - start, lower);
-  hashes[idx] = h;
-}
-
-// Whether spec `s` applies to a line of event `event`: a header variable
-// always does, a content variable when it is scoped to no event or to this one.
-static __device__ __forceinline__ int watch_relevant(const WatchSpec s,
-                                                     int event) {
-  return s.kind != 0 || s.event < 0 || event == s.event;
-}
-
-// Hash of the span that spec `s` watches on `line`: 0 when the spec is not
-// relevant for the line or the field is absent. The same lookup as in
-// dmx_watch_hashes, which keeps its own copy: routed through this helper it
-// compiles to two more scalar instructions, and the watches-only path is
-// kept instruction for instruction what it was.
-static __device__ __forceinline__ unsigned long long watch_span_hash(
-    const WatchSpec s, int line,
-    const unsigned char* __restrict__ lines, int max_len,
-    const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps, int lower) {
-  unsigned long long h = 0ull;
-  int start = -1, end = -1;
-  if (s.kind == 0) {
-    if ((s.event < 0 || event_id[line] == s.event) && s.pos < n_caps[line]) {
-      start = caps[((long)line * max_caps + s.pos) * 2];
-      end = caps[((long)line * max_caps + s.pos) * 2 + 1];
-    }
-  } else {
-    if (n_fmt_caps && s.pos < n_fmt_caps[line]) {
-      start = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2];
-      end = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2 + 1];
-    }
-  }
-  if (start >= 0 && end >= start)
-    h = fnv1a64(lines + (long)line * max_len + start, end - start, lower);
-  return h;
+  if (idx >= (long)batch.B * W) return;
+  hashes[idx] = field_hash(batch, specs[idx % W], idx / W, lower);
 }
 
 // Watches and combinations in one launch. For each (line, column) of
@@ -115,44 +52,34 @@ static __device__ __forceinline__ unsigned long long watch_span_hash(
 // the hash of combination c (docs/kernels.md, "Combination hash"): every
 // member's relevance bit and the 8 bytes of its span hash, low byte first,
 // folded FNV-1a style in member order and forced odd, or 0 when no member
-// is relevant for the line. members [M, 4] holds WatchSpec rows, combo c
+// is relevant for the line. members [M, 4] holds FieldSpec rows, combo c
 // owns rows combo_off[c] .. combo_off[c + 1]; the host guarantees offsets
 // in [0, M] (ops.pack_combos), the clamp keeps a broken promise in bounds.
 extern "C" __global__ __launch_bounds__(256)
 void dmx_watch_combo_hashes(
-    const unsigned char* __restrict__ lines, int max_len,
-    const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps,
-    const WatchSpec* __restrict__ specs, int W,
-    const WatchSpec* __restrict__ members, int M,
-    const int* __restrict__ combo_off, int C,
-    int B, int lower,
+    const ParsedBatch batch, const FieldSpec* __restrict__ specs, int W,
+    const FieldSpec* __restrict__ members, int M,
+    const int* __restrict__ combo_off, int C, int lower,
     unsigned long long* __restrict__ hashes) {  // [B, W + C]
   const int cols = W + C;
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (long)B * cols) return;
+  if (gid >= (long)batch.B * cols) return;
   const int idx = (int)gid;
   const int line = idx / cols;
   const int col = idx % cols;
   if (col < W) {
-    hashes[idx] = watch_span_hash(specs[col], line, lines, max_len, event_id,
-                                  caps, n_caps, max_caps, fmt_caps, n_fmt_caps,
-                                  max_fmt_caps, lower);
+    hashes[idx] = field_hash(batch, specs[col], line, lower);
     return;
   }
-  const int event = event_id[line];
+  const int event = batch.event_id[line];
   const int m0 = max(combo_off[col - W], 0);
   const int m1 = min(combo_off[col - W + 1], M);
   unsigned long long h = 1469598103934665603ull;
   int any = 0;
   for (int m = m0; m < m1; ++m) {
-    const WatchSpec s = members[m];
-    const int relevant = watch_relevant(s, event);
-    unsigned long long mh = watch_span_hash(
-        s, line, lines, max_len, event_id, caps, n_caps, max_caps, fmt_caps,
-        n_fmt_caps, max_fmt_caps, lower);
+    const FieldSpec s = members[m];
+    const int relevant = field_relevant(s, event);
+    unsigned long long mh = field_hash(batch, s, line, lower);
     any |= relevant;
     h = (h ^ (unsigned long long)relevant) * 1099511628211ull;
     for (int b = 0; b < 8; ++b) {
@@ -210,34 +137,25 @@ void dmx_hashset_probe(
 }
 
 extern "C" void dmx_launch_watch_hashes(
-    const uint8_t* lines, int max_len, const int32_t* event_id,
-    const int32_t* caps, const int32_t* n_caps, int max_caps,
-    const int32_t* fmt_caps, const int32_t* n_fmt_caps, int max_fmt_caps,
-    const int32_t* specs, int W, int B, int lower, int64_t* hashes,
+    ParsedBatch batch, const int32_t* specs, int W, int lower, int64_t* hashes,
     hipStream_t stream) {
-  const long total = (long)B * W;
+  const long total = (long)batch.B * W;
   const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(dmx_watch_hashes, dim3(grid), dim3(256), 0, stream,
-                     lines, max_len, event_id, caps, n_caps, max_caps,
-                     fmt_caps, n_fmt_caps, max_fmt_caps,
-                     (const WatchSpec*)specs, W, B, lower,
+  hipLaunchKernelGGL(dmx_watch_hashes, dim3(grid), dim3(256), 0, stream, batch,
+                     (const FieldSpec*)specs, W, lower,
                      (unsigned long long*)hashes);
 }
 
 extern "C" void dmx_launch_watch_combo_hashes(
-    const uint8_t* lines, int max_len, const int32_t* event_id,
-    const int32_t* caps, const int32_t* n_caps, int max_caps,
-    const int32_t* fmt_caps, const int32_t* n_fmt_caps, int max_fmt_caps,
-    const int32_t* specs, int W, const int32_t* members, int M,
-    const int32_t* combo_off, int C, int B, int lower, int64_t* hashes,
+    ParsedBatch batch, const int32_t* specs, int W, const int32_t* members,
+    int M, const int32_t* combo_off, int C, int lower, int64_t* hashes,
     hipStream_t stream) {
-  const long total = (long)B * (W + C);
+  const long total = (long)batch.B * (W + C);
   const int grid = (int)((total + 255) / 256);
   hipLaunchKernelGGL(dmx_watch_combo_hashes, dim3(grid), dim3(256), 0, stream,
-                     lines, max_len, event_id, caps, n_caps, max_caps,
-                     fmt_caps, n_fmt_caps, max_fmt_caps,
-                     (const WatchSpec*)specs, W, (const WatchSpec*)members, M,
-                     combo_off, C, B, lower, (unsigned long long*)hashes);
+                     batch, (const FieldSpec*)specs, W,
+                     (const FieldSpec*)members, M, combo_off, C, lower,
+                     (unsigned long long*)hashes);
 }
 
 extern "C" void dmx_launch_hashset_insert(

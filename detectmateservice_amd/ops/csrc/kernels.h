@@ -91,6 +91,20 @@ constexpr int64_t bert_fused_fb_elems(int n_layers) {
   return (int64_t)n_layers * FB_SIZE + 1;
 }
 
+// ---- the parsed batch --------------------------------------------------------
+// What dmx_template_match wrote for B lines of max_len bytes, as the field
+// kernels read it (field_span.h; docs/kernels.md, "Parsed batch and field
+// span"). Passed by value, to the launchers and on to the kernels.
+struct ParsedBatch {
+  const uint8_t* lines;       // [B, max_len]
+  const int32_t* event_id;    // [B]
+  const int32_t* caps;        // [B, max_caps, 2] (start, end) per capture
+  const int32_t* n_caps;      // [B]
+  const int32_t* fmt_caps;    // [B, max_fmt_caps, 2] header fields
+  const int32_t* n_fmt_caps;  // [B]
+  int B, max_len, max_caps, max_fmt_caps;
+};
+
 // ---- launchers --------------------------------------------------------------
 // Each enqueues on `stream` of the CURRENT device and does not synchronize.
 // The void ones report failure through hipGetLastError(); the fused-BERT
@@ -166,26 +180,15 @@ void dmx_launch_template_match(
     hipStream_t stream);
 
 // hashset.hip (specs: [W, 4] int32 = kind, event, pos, pad)
-void dmx_launch_watch_hashes(const uint8_t* lines, int max_len,
-                             const int32_t* event_id, const int32_t* caps,
-                             const int32_t* n_caps, int max_caps,
-                             const int32_t* fmt_caps,
-                             const int32_t* n_fmt_caps, int max_fmt_caps,
-                             const int32_t* specs, int W, int B, int lower,
-                             int64_t* hashes, hipStream_t stream);
+void dmx_launch_watch_hashes(ParsedBatch batch, const int32_t* specs, int W,
+                             int lower, int64_t* hashes, hipStream_t stream);
 // hashes [B, W + C]: the W watch columns, then one column per combination.
 // members: [M, 4] int32 rows laid out like specs; combo_off: [C + 1] int32,
 // combination c owns member rows combo_off[c] .. combo_off[c + 1].
-void dmx_launch_watch_combo_hashes(const uint8_t* lines, int max_len,
-                                   const int32_t* event_id,
-                                   const int32_t* caps, const int32_t* n_caps,
-                                   int max_caps, const int32_t* fmt_caps,
-                                   const int32_t* n_fmt_caps,
-                                   int max_fmt_caps, const int32_t* specs,
+void dmx_launch_watch_combo_hashes(ParsedBatch batch, const int32_t* specs,
                                    int W, const int32_t* members, int M,
-                                   const int32_t* combo_off, int C, int B,
-                                   int lower, int64_t* hashes,
-                                   hipStream_t stream);
+                                   const int32_t* combo_off, int C, int lower,
+                                   int64_t* hashes, hipStream_t stream);
 void dmx_launch_hashset_insert(const int64_t* hashes, int64_t* tables, int B,
                                int W, int capacity, hipStream_t stream);
 void dmx_launch_hashset_probe(const int64_t* hashes, const int64_t* tables,
@@ -213,14 +216,9 @@ void dmx_launch_event_rate(const int32_t* event_id, const int32_t* n_valid,
 // is not a number alerts). slack f64 [R], read only. State, updated in
 // place: lo, hi f64 [R]; n int64 [R]. Outputs, fully written: range_code
 // int32 [B, R], range_value f64 [B, R].
-void dmx_launch_value_range(const uint8_t* lines, int max_len,
-                            const int32_t* event_id, const int32_t* caps,
-                            const int32_t* n_caps, int max_caps,
-                            const int32_t* fmt_caps,
-                            const int32_t* n_fmt_caps, int max_fmt_caps,
-                            const int32_t* specs, int R, const double* slack,
-                            double* lo, double* hi, int64_t* n, int B,
-                            int train_upto, int32_t* range_code,
+void dmx_launch_value_range(ParsedBatch batch, const int32_t* specs, int R,
+                            const double* slack, double* lo, double* hi,
+                            int64_t* n, int train_upto, int32_t* range_code,
                             double* range_value, hipStream_t stream);
 
 // edit_distance.hip

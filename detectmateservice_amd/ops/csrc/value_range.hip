@@ -18,6 +18,7 @@
 // same for every schedule and the stage is graph-capturable.
 #include <hip/hip_runtime.h>
 
+#include "field_span.h"
 #include "kernels.h"
 
 // lo - slack * (hi - lo) and hi + slack * (hi - lo) must round like the CPU
@@ -29,22 +30,14 @@ namespace {
 constexpr int VR_THREADS = 256;
 constexpr int VR_WAVES = VR_THREADS / 64;
 
-// WatchSpec's layout (hashset.hip) with the pad word used as flags.
-struct RangeSpec {
-  int kind;   // 0 = content variable (caps), 1 = header variable (fmt_caps)
-  int event;  // kind 0 only: < 0 = any event
-  int pos;
-  int flags;  // bit 0: a present field that is not a number gets code 3
-};
-
 struct Parsed {
   int present;  // the range is relevant for the line and the field is there
   int number;   // ... and the span matches the grammar
   double v;     // its value, 0 otherwise
 };
 
-// The span lookup of dmx_watch_hashes (this file keeps its own copy, as the
-// combination kernel does), then the decimal parse.
+// The decimal number in p[0 .. len), len >= 0: whether the bytes match the
+// grammar, and the value into *v when they do.
 //
 // Grammar: [+-]?[0-9]+(\.[0-9]+)? over the whole span, at most VR_MAX_DIGITS
 // digits, at most VR_MAX_SPAN bytes. Value: M / 10^k with M the integer of
@@ -52,40 +45,12 @@ struct Parsed {
 // 10^k <= 10^14 are both exact in f64, so the one division is the correctly
 // rounded value of the decimal string. -0 is never produced.
 //
-// Reads: pos is checked against both the row's capture count and the table
-// width, the span against [0, max_len], and a span longer than VR_MAX_SPAN
-// is rejected before its first byte is loaded.
-__device__ __forceinline__ Parsed vr_parse(
-    const RangeSpec s, int line, const unsigned char* __restrict__ lines,
-    int max_len, const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps) {
-  Parsed out;
-  out.present = 0;
-  out.number = 0;
-  out.v = 0.0;
-  int start = -1, end = -1;
-  if (s.pos >= 0) {
-    if (s.kind == 0) {
-      if ((s.event < 0 || event_id[line] == s.event) &&
-          s.pos < min(n_caps[line], max_caps)) {
-        start = caps[((long)line * max_caps + s.pos) * 2];
-        end = caps[((long)line * max_caps + s.pos) * 2 + 1];
-      }
-    } else {
-      if (s.pos < min(n_fmt_caps[line], max_fmt_caps)) {
-        start = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2];
-        end = fmt_caps[((long)line * max_fmt_caps + s.pos) * 2 + 1];
-      }
-    }
-  }
-  if (start < 0 || end < start || end > max_len) return out;
-  out.present = 1;
-  const int len = end - start;
-  if (len == 0 || len > VR_MAX_SPAN) return out;
+// Reads: an empty span and one longer than VR_MAX_SPAN are rejected before
+// their first byte is loaded.
+__device__ __forceinline__ int parse_decimal(const unsigned char* p, int len,
+                                             double* v) {
+  if (len == 0 || len > VR_MAX_SPAN) return 0;
 
-  const unsigned char* p = lines + (long)line * max_len + start;
   int i = 0, negative = 0;
   const unsigned char c0 = p[0];
   if (c0 == '+' || c0 == '-') {
@@ -113,10 +78,21 @@ __device__ __forceinline__ Parsed vr_parse(
   }
   if (!ok || n_int == 0 || (dot && n_frac == 0) ||
       n_int + n_frac > VR_MAX_DIGITS)
-    return out;
-  out.number = 1;
-  const double v = (double)M / (double)scale;
-  out.v = (negative && M != 0) ? -v : v;
+    return 0;
+  const double q = (double)M / (double)scale;
+  *v = (negative && M != 0) ? -q : q;
+  return 1;
+}
+
+// The field that spec `s` names on `line` (field_span.h), read as a number.
+__device__ __forceinline__ Parsed vr_parse(const ParsedBatch& batch,
+                                           const FieldSpec s, int line) {
+  Parsed out = {0, 0, 0.0};
+  const FieldSpan f = field_span(batch, s, line);
+  if (f.len < 0) return out;
+  out.present = 1;
+  out.number = parse_decimal(
+      batch.lines + (long)line * batch.max_len + f.start, f.len, &out.v);
   return out;
 }
 
@@ -128,12 +104,7 @@ __device__ __forceinline__ Parsed vr_parse(
 // with plain stores. No other block touches range r.
 extern "C" __global__ __launch_bounds__(VR_THREADS)
 void dmx_value_range_fit(
-    const unsigned char* __restrict__ lines, int max_len,
-    const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps,
-    const RangeSpec* __restrict__ specs,
+    const ParsedBatch batch, const FieldSpec* __restrict__ specs,
     int train_upto,                // <= B, checked by the binding
     double* __restrict__ lo,       // [R]
     double* __restrict__ hi,       // [R]
@@ -143,12 +114,11 @@ void dmx_value_range_fit(
   __shared__ int s_n[VR_WAVES];
   const int r = blockIdx.x;
   const int tid = threadIdx.x;
-  const RangeSpec s = specs[r];
+  const FieldSpec s = specs[r];
   double t_lo = INFINITY, t_hi = -INFINITY;
   int t_n = 0;
   for (int line = tid; line < train_upto; line += VR_THREADS) {
-    const Parsed f = vr_parse(s, line, lines, max_len, event_id, caps, n_caps,
-                              max_caps, fmt_caps, n_fmt_caps, max_fmt_caps);
+    const Parsed f = vr_parse(batch, s, line);
     if (f.number) {
       t_lo = f.v < t_lo ? f.v : t_lo;
       t_hi = f.v > t_hi ? f.v : t_hi;
@@ -184,26 +154,20 @@ void dmx_value_range_fit(
 
 extern "C" __global__ __launch_bounds__(VR_THREADS)
 void dmx_value_range_judge(
-    const unsigned char* __restrict__ lines, int max_len,
-    const int* __restrict__ event_id,
-    const int* __restrict__ caps, const int* __restrict__ n_caps, int max_caps,
-    const int* __restrict__ fmt_caps, const int* __restrict__ n_fmt_caps,
-    int max_fmt_caps,
-    const RangeSpec* __restrict__ specs, int R,
+    const ParsedBatch batch, const FieldSpec* __restrict__ specs, int R,
     const double* __restrict__ slack,  // [R]
     const double* __restrict__ lo,     // [R]
     const double* __restrict__ hi,     // [R]
-    int B, int train_upto,
+    int train_upto,
     int* __restrict__ range_code,        // [B, R]
     double* __restrict__ range_value) {  // [B, R]
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (long)B * R) return;
+  if (gid >= (long)batch.B * R) return;
   const int idx = (int)gid;  // B * R < 2^31, checked by the binding
   const int line = idx / R;
   const int r = idx % R;
-  const RangeSpec s = specs[r];
-  const Parsed f = vr_parse(s, line, lines, max_len, event_id, caps, n_caps,
-                            max_caps, fmt_caps, n_fmt_caps, max_fmt_caps);
+  const FieldSpec s = specs[r];
+  const Parsed f = vr_parse(batch, s, line);
   int code = 0;
   if (line >= train_upto && f.present) {
     if (!f.number) {
@@ -225,23 +189,16 @@ void dmx_value_range_judge(
 }
 
 extern "C" void dmx_launch_value_range(
-    const uint8_t* lines, int max_len, const int32_t* event_id,
-    const int32_t* caps, const int32_t* n_caps, int max_caps,
-    const int32_t* fmt_caps, const int32_t* n_fmt_caps, int max_fmt_caps,
-    const int32_t* specs, int R, const double* slack, double* lo, double* hi,
-    int64_t* n, int B, int train_upto, int32_t* range_code,
+    ParsedBatch batch, const int32_t* specs, int R, const double* slack,
+    double* lo, double* hi, int64_t* n, int train_upto, int32_t* range_code,
     double* range_value, hipStream_t stream) {
   if (train_upto > 0)
     hipLaunchKernelGGL(dmx_value_range_fit, dim3(R), dim3(VR_THREADS), 0,
-                       stream, lines, max_len, event_id, caps, n_caps,
-                       max_caps, fmt_caps, n_fmt_caps, max_fmt_caps,
-                       (const RangeSpec*)specs, train_upto, lo, hi,
-                       (long long*)n);
-  const long total = (long)B * R;
+                       stream, batch, (const FieldSpec*)specs, train_upto, lo,
+                       hi, (long long*)n);
+  const long total = (long)batch.B * R;
   const int grid = (int)((total + VR_THREADS - 1) / VR_THREADS);
   hipLaunchKernelGGL(dmx_value_range_judge, dim3(grid), dim3(VR_THREADS), 0,
-                     stream, lines, max_len, event_id, caps, n_caps, max_caps,
-                     fmt_caps, n_fmt_caps, max_fmt_caps,
-                     (const RangeSpec*)specs, R, slack, lo, hi, B, train_upto,
-                     range_code, range_value);
+                     stream, batch, (const FieldSpec*)specs, R, slack, lo, hi,
+                     train_upto, range_code, range_value);
 }
