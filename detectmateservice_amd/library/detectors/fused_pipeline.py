@@ -66,6 +66,13 @@ class FusedPipelineDetectorConfig(CoreConfig):
     line_buffer_bytes: int = 0
 
 
+def _id_of(ids_blob, ids_off):
+    """i -> logID of row i, decoded lazily from the packed ids (alerts are
+    rare)."""
+    return lambda i: ids_blob[int(ids_off[i]):int(ids_off[i + 1])].decode(
+        "utf-8", "replace")
+
+
 class FusedPipelineDetector(CoreComponent):
     CONFIG_CLASS = FusedPipelineDetectorConfig
 
@@ -137,18 +144,9 @@ class FusedPipelineDetector(CoreComponent):
         lines, lens = self.line_buffer.window(lines_back)
         if lines.shape[0] == 0:
             return {"rescored": 0, "anomalies": 0}
-        old_thr = self.pipe.config.score_threshold
-        if threshold is not None:
-            self.pipe.config.score_threshold = float(threshold)
-        try:
-            seen = self.pipe.seen_lines  # rescoring must not advance
-            # force detect mode: a rescore during the training phase must
-            # not INSERT window values into the live hash sets
-            self.pipe.seen_lines = max(seen, self.pipe.config.train_lines)
-            out = self.pipe.process_packed(lines, lens, rate=False)
-        finally:
-            self.pipe.seen_lines = seen
-            self.pipe.config.score_threshold = old_thr
+        # detect mode whatever the phase: a rescore during the training phase
+        # must not INSERT window values into the live hash sets
+        out = self.pipe.rescore(lines, lens, threshold)
         n = int(lines.shape[0])
         return {
             "rescored": n,
@@ -165,7 +163,7 @@ class FusedPipelineDetector(CoreComponent):
         if (gb > 0 and self.device.type == "cuda"
                 and self.pipe.seen_lines >= self.config.data_use_training
                 and lines.shape[0] <= gb):
-            if self.pipe._graph is None:
+            if not self.pipe.graph_enabled:
                 self.pipe.enable_graph(gb)
             if self.line_buffer is not None:
                 self.line_buffer.append(lines.to(self.device, non_blocking=True),
@@ -185,30 +183,14 @@ class FusedPipelineDetector(CoreComponent):
             return []
         idxs = torch.nonzero(anomaly, as_tuple=False).flatten().cpu().tolist()
         scores = out["scores"].float().cpu()
-        nv = out["nv_unseen"].cpu() if out["nv_unseen"] is not None else None
-        combo = out.get("combo_unseen")
-        combo = combo.cpu() if combo is not None else None
-        rate_hits = out.get("rate_hits")
-        rate_hits = rate_hits.cpu() if rate_hits is not None else None
-        range_code = out.get("range_code")
-        range_code = range_code.cpu() if range_code is not None else None
+        # each stage's own keys move to the host once per alerting batch
+        host = {"scores": scores}
+        host.update((k, out[k].cpu()) for s in self.pipe.stages for k in s.keys
+                    if out.get(k) is not None)
         now = int(time.time())
         alerts = []
         for i in idxs:
-            reasons = []
-            if nv is not None and int(nv[i].sum()) > 0:
-                reasons.append("unknown watched value")
-            if combo is not None and int(combo[i].sum()) > 0:
-                reasons.append("unknown combination")
-            if rate_hits is not None and int(rate_hits[i]) > 0:
-                reasons.append(self._rate_reason(out, i))
-            if range_code is not None and bool(range_code[i].any()):
-                reasons.extend(self._range_reasons(out, range_code, i))
-            if (self.pipe.model is not None
-                    and float(scores[i]) > self.config.score_threshold):
-                what = ("embedding distance"
-                        if self.pipe.embedding_stats is not None else "score")
-                reasons.append(f"{what} {float(scores[i]):.3f}")
+            reasons = [r for s in self.pipe.stages for r in s.reasons(host, i)]
             lid = id_of(i)
             alerts.append((i, DetectorSchema(
                 detectorID=self.detector_id,
@@ -221,49 +203,12 @@ class FusedPipelineDetector(CoreComponent):
             ).serialize()))
         return alerts
 
-    @staticmethod
-    def _rate_reason(out, i: int) -> str:
-        """"event rate: event 3: 950/window (z=+12.3); ..." for boundary row
-        i: the flagged bins of the window that row completed."""
-        slot = int(out["rate_slot"][i])
-        counts = out["rate_counts"][slot].cpu()
-        z = out["rate_z"][slot].cpu()
-        parts = []
-        for e in torch.nonzero(z, as_tuple=False).flatten().tolist():
-            who = "unparsed" if e == 0 else f"event {e}"
-            parts.append(f"{who}: {int(counts[e])}/window (z={float(z[e]):+.1f})")
-        return "event rate: " + "; ".join(parts)
-
-    def _range_reasons(self, out, range_code, i: int) -> List[str]:
-        """"value out of range: bytes = 18234511 above [0, 1048576]" or "not
-        a number: bytes" for every flagged range of row i. The bounds are
-        read from the device state here, when an alert is worded, and
-        nowhere on the hot path."""
-        state = self.pipe.value_ranges
-        lo, hi = state.lo.cpu(), state.hi.cpu()
-        reasons = []
-        for r in torch.nonzero(range_code[i], as_tuple=False).flatten().tolist():
-            code, name = int(range_code[i, r]), state.names[r]
-            if code == 3:
-                reasons.append(f"not a number: {name}")
-                continue
-            side = "below" if code == 1 else "above"
-            reasons.append(
-                f"value out of range: {name} = {float(out['range_value'][i, r]):.15g} "
-                f"{side} [{float(lo[r]):.15g}, {float(hi[r]):.15g}]")
-        return reasons
-
     def process_packed_frames(self, lines, lens, ids_blob, ids_off) -> List:
         """Engine packed-loop entry: tensors in (already decoded by the
         C++ socket reader), [(idx, alert bytes)] out."""
         if lines.shape[0] == 0:
             return []
-        out = self._score_packed(lines, lens)
-        return self._alerts(
-            out,
-            lambda i: ids_blob[int(ids_off[i]):int(ids_off[i + 1])].decode(
-                "utf-8", "replace"),
-        )
+        return self._alerts(self._score_packed(lines, lens), _id_of(ids_blob, ids_off))
 
     # -- pipelined packed path (submit/collect) ------------------------
     # The engine overlaps batch N's GPU work with batch N+1's recv+decode:
@@ -273,13 +218,11 @@ class FusedPipelineDetector(CoreComponent):
         if lines.shape[0] == 0:
             return None
         out = self._score_packed(lines, lens)  # async: kernels queued
-        if self.pipe._graph is not None:
+        if self.pipe.graph_enabled:
             # graph replay writes into STATIC buffers: clone (async) so
             # the next submit's replay can't clobber this batch's outputs
-            out = {
-                k: (v.clone() if torch.is_tensor(v) else v)
-                for k, v in out.items() if k != "match"
-            }
+            out = {k: (v.clone() if torch.is_tensor(v) else v)
+                   for k, v in out.items() if k != "match"}
         # keep `lines` alive until the async H2D copy completes (the
         # pinned block would otherwise return to the cache mid-copy)
         return (out, ids_blob, ids_off, lines)
@@ -288,11 +231,7 @@ class FusedPipelineDetector(CoreComponent):
         if token is None:
             return []
         out, ids_blob, ids_off, _lines = token
-        return self._alerts(
-            out,
-            lambda i: ids_blob[int(ids_off[i]):int(ids_off[i + 1])].decode(
-                "utf-8", "replace"),
-        )
+        return self._alerts(out, _id_of(ids_blob, ids_off))
 
     def process_batch(self, frames: List[bytes]) -> List[Optional[bytes]]:
         if not frames:
@@ -310,15 +249,13 @@ class FusedPipelineDetector(CoreComponent):
                 list(frames), self.config.max_len,
                 self.device.type == "cuda",
             )
-            log_ids_raw = (ids_blob, ids_off)
-            log_ids = None  # decoded lazily, only for alert frames
+            id_of = _id_of(ids_blob, ids_off)
         else:
             logs = [LogSchema.deserialize(f) for f in frames]
             lines, lens = ops.pack_lines(
                 [(l.log or "").encode() for l in logs], self.config.max_len
             )
-            log_ids_raw = None
-            log_ids = [l.logID for l in logs]
+            id_of = [l.logID for l in logs].__getitem__
         _t1 = time.perf_counter() if _stats else 0.0
         out = self._score_packed(lines, lens)
         if _stats:
@@ -336,86 +273,18 @@ class FusedPipelineDetector(CoreComponent):
                     self._stat_acc[1] * 1e3 / self._stat_acc[0],
                     self._stat_acc[2] * 1e3 / self._stat_acc[0],
                 )
-        if log_ids is None:
-            blob, off = log_ids_raw
-            id_of = lambda i: blob[int(off[i]):int(off[i + 1])].decode(  # noqa: E731
-                "utf-8", "replace")
-        else:
-            id_of = lambda i: log_ids[i]  # noqa: E731
         results: List[Optional[bytes]] = [None] * len(frames)
         for i, alert in self._alerts(out, id_of):
             results[i] = alert
         return results
 
-    # -- checkpoint -----------------------------------------------------
+    # -- checkpoint: the pipeline owns the state ---------------------------
     def dist_sync(self, group=None) -> None:
-        """COLLECTIVE merge of the data-parallel GPU hash sets (one
-        batched insert-kernel call per peer table —
-        parallel/dist.py::all_reduce_hashsets). Event-rate state is left
-        alone: each rank judges the rate of its own shard of the stream.
-        Value ranges are merged: lo by MIN, hi by MAX, n by SUM."""
-        import torch.distributed as tdist
-
-        if not tdist.is_initialized() or tdist.get_world_size(group) <= 1:
-            return
-        self._sync_value_ranges(group)
-        if self.pipe.hashsets is None:
-            return
-        hs = self.pipe.hashsets
-        if hasattr(hs, "tables"):  # GPU open-addressing tables
-            from ...parallel import dist as dmx_dist
-
-            dmx_dist.all_reduce_hashsets(hs.tables, group=group)
-        else:  # CPU fallback keeps Python sets
-            world = tdist.get_world_size(group)
-            local = [sorted(s) for s in hs.sets]
-            gathered: list = [None] * world
-            tdist.all_gather_object(gathered, local, group=group)
-            me = tdist.get_rank(group)
-            for r, other in enumerate(gathered):
-                if r == me or not other:
-                    continue
-                for w, values in enumerate(other):
-                    hs.sets[w].update(values)
-
-    def _sync_value_ranges(self, group=None) -> None:
-        """COLLECTIVE: every rank ends with the smallest lo, the largest hi
-        and the summed n of all ranks, written into the tensors the kernels
-        (and a captured graph) read."""
-        import torch.distributed as tdist
-
-        state = self.pipe.value_ranges
-        if state is None:
-            return
-        lo, hi, n = state.lo.clone(), state.hi.clone(), state.n.clone()
-        tdist.all_reduce(lo, op=tdist.ReduceOp.MIN, group=group)
-        tdist.all_reduce(hi, op=tdist.ReduceOp.MAX, group=group)
-        tdist.all_reduce(n, op=tdist.ReduceOp.SUM, group=group)
-        state.merge_(lo, hi, n - state.n)  # n: the other ranks' share
+        """COLLECTIVE merge of the data-parallel stage state."""
+        self.pipe.dist_sync(group)
 
     def state_dict(self) -> Dict[str, Any]:
-        state: Dict[str, Any] = {"seen_lines": self.pipe.seen_lines}
-        if self.pipe.hashsets is not None:
-            state["hashsets"] = self.pipe.hashsets.state_dict()
-        if self.pipe.model is not None:
-            state["model"] = self.pipe.model.state_dict()
-        if self.pipe.embedding_stats is not None:
-            state["embedding_stats"] = self.pipe.embedding_stats.state_dict()
-        if self.pipe.event_rate is not None:
-            state["event_rate"] = self.pipe.event_rate.state_dict()
-        if self.pipe.value_ranges is not None:
-            state["value_ranges"] = self.pipe.value_ranges.state_dict()
-        return state
+        return self.pipe.state_dict()
 
     def load_state_dict(self, state: Dict[str, Any]) -> None:
-        self.pipe.seen_lines = int(state.get("seen_lines", 0))
-        if "hashsets" in state and self.pipe.hashsets is not None:
-            self.pipe.hashsets.load_state_dict(state["hashsets"])
-        if "model" in state and self.pipe.model is not None:
-            self.pipe.model.load_state_dict(state["model"])
-        if "embedding_stats" in state and self.pipe.embedding_stats is not None:
-            self.pipe.embedding_stats.load_state_dict(state["embedding_stats"])
-        if "event_rate" in state and self.pipe.event_rate is not None:
-            self.pipe.event_rate.load_state_dict(state["event_rate"])
-        if "value_ranges" in state and self.pipe.value_ranges is not None:
-            self.pipe.value_ranges.load_state_dict(state["value_ranges"])
+        self.pipe.load_state_dict(state)

@@ -8,50 +8,27 @@ HIP stream. The socket Service path (core.py) remains for distributed /
 edge deployment; this class is what bench.py drives and what a
 TransformerDetector service uses internally per batch.
 
-Stage structure per batch (all on `device`):
-  1. template_match kernel: log_format header split + template match
-     (event_id + capture spans)
-  2. NewValue watch: hash watched spans (kernel) -> probe GPU hash sets
-     (training batches insert instead). With ``combos`` configured the same
-     launch also hashes each combination of fields (docs/kernels.md,
-     "Combination hash") and the same probe covers watches and combos.
-  3. Transformer scorer (BERT-tiny bf16 MFMA) over content-span byte tokens
-  4. With ``event_rate`` configured: per-event line counts in windows of
-     ``window_lines`` lines against an EWMA baseline (docs/kernels.md,
-     "Event-rate windows"). The only stage whose verdict is about the stream
-     and not about one line: its state lives on the device and the line that
-     completes a window carries the alert.
-  5. With ``ranges`` configured: each range's field is parsed as a decimal
-     number from the line bytes and judged against the smallest and largest
-     value seen in training (docs/kernels.md, "Value ranges"); one launch in
-     the steady state, state on the device.
+Per batch, all on `device`: the template_match kernel (log_format header
+split + template match: event_id + capture spans), then the configured stages
+of stages.py, ``pipe.stages``, in this order: new value (watches and
+combinations), event rate, value ranges, transformer score. Launches, alert
+reasons and checkpoint keys follow that list; each stage class says what it
+computes.
 Anomaly = NewValue unseen-value hit OR unseen combination OR transformer
 score > threshold OR, on a window's boundary line, a flagged event rate OR a
 numeric field outside its learned range.
-
-``score_mode`` says what the transformer score is. ``"head"`` (default) is
-the model's linear score head. ``"embedding"`` is the distance of the line's
-mean-pooled embedding from a diagonal Gaussian fitted to the training-phase
-rows (``EmbeddingStats``): those rows update the moments and score 0, later
-rows score ``sqrt(mean_i((x_i - mu_i)^2 / var_i))``, one launch of the fused
-kernel's distance head per batch and no [B, hidden] write. An empty content
-span is far from any trained distribution, so it alerts (about 11.5 on the
-audit-log generator against a normal maximum of about 1.3).
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Any, Dict, Optional, Sequence
 
 import torch
 
 from . import ops
-from .models.bert_tiny import (
-    BertTinyConfig,
-    BertTinyDetectorModel,
-    EmbeddingStats,
-)
+from .models.bert_tiny import BertTinyConfig
+from .stages import (EventRateStage, NewValueStage, TransformerStage,
+                     ValueRangeStage, marked)
 
 
 @dataclass
@@ -90,81 +67,38 @@ class PipelineConfig:
 
 
 class GpuPipeline:
-    #: event-rate outputs; the last two are per window slot, [NW, E], not per
-    #: line
-    _RATE_KEYS = ("rate_hits", "rate_slot", "rate_counts", "rate_z")
-    _PER_SLOT_KEYS = ("rate_counts", "rate_z")
+    _RATE_KEYS = EventRateStage.keys
 
     def __init__(self, config: PipelineConfig, device: str | torch.device = "cpu") -> None:
         self.config = config
         self.device = torch.device(device)
         self.matcher = ops.TemplateMatcher(
-            config.templates,
-            log_format=config.log_format,
-            lowercase=config.lowercase,
-            device=self.device,
-            max_len=config.max_len,
-        )
-        specs = [ops.watch_spec_row(w) for w in config.watches]
-        self.specs = (
-            torch.tensor(specs, dtype=torch.int32, device=self.device)
-            if specs
-            else torch.zeros((0, 4), dtype=torch.int32, device=self.device)
-        )
-        # combinations: CSR member table, validated on the host before upload
-        self.n_combos = len(config.combos)
-        self.members = self.combo_off = None
-        if self.n_combos:
-            members, combo_off = ops.pack_combos(config.combos)
-            self.members = members.to(self.device)
-            self.combo_off = combo_off.to(self.device)
-        # one table per watch, then one per combination
-        n_tables = len(specs) + self.n_combos
-        self.hashsets = (
-            ops.GpuHashSets(n_tables, config.hashset_capacity, device=self.device)
-            if n_tables
-            else None
-        )
-        self.model = (
-            BertTinyDetectorModel(config.bert, device=self.device, seed=config.seed)
-            if config.use_transformer
-            else None
-        )
+            config.templates, log_format=config.log_format,
+            lowercase=config.lowercase, device=self.device, max_len=config.max_len)
         if config.score_mode not in ("head", "embedding"):
             raise ValueError(
                 f"score_mode must be 'head' or 'embedding', got {config.score_mode!r}")
-        if config.score_mode == "embedding" and self.model is None:
+        if config.score_mode == "embedding" and not config.use_transformer:
             raise ValueError("score_mode 'embedding' needs use_transformer")
-        self.embedding_stats = (
-            EmbeddingStats(config.bert.hidden, device=self.device)
-            if config.score_mode == "embedding"
-            else None
-        )
-        self.event_rate: Optional[ops.EventRateState] = None
-        if config.event_rate is not None:
-            unknown = set(config.event_rate) - set(ops.EVENT_RATE_DEFAULTS)
-            if unknown:
-                raise ValueError(
-                    f"unknown event_rate key(s) {sorted(unknown)}; valid keys: "
-                    f"{sorted(ops.EVENT_RATE_DEFAULTS)}")
-            self.event_rate = ops.EventRateState(
-                len(self.matcher.templates), device=self.device,
-                **{**ops.EVENT_RATE_DEFAULTS, **config.event_rate})
-        self.value_ranges: Optional[ops.ValueRangeState] = (
-            ops.ValueRangeState(list(config.ranges), device=self.device)
-            if len(config.ranges) else None
-        )
+        nv = NewValueStage(config, self.device)
+        rate = (EventRateStage(config, self.device, len(self.matcher.templates))
+                if config.event_rate is not None else None)
+        ranges = ValueRangeStage(config, self.device) if len(config.ranges) else None
+        bert = TransformerStage(config, self.device) if config.use_transformer else None
+        # the state objects under their public names (None = not configured)
+        self.specs, self.members, self.combo_off, self.n_combos = (
+            nv.specs, nv.members, nv.combo_off, nv.n_combos)
+        self.hashsets, self.event_rate, self.value_ranges, self.model = (
+            s.state if s else None for s in (nv, rate, ranges, bert))
+        self.embedding_stats = bert.stats if bert else None
+        self.stages = [s for s in (nv if nv.state is not None else None,
+                                   rate, ranges, bert) if s is not None]
         self.seen_lines = 0
         # hipGraph capture state (enable_graph(); steady-state detect only)
-        self._graph = None
-        self._graph_in: Optional[tuple] = None
-        self._graph_out: Optional[Dict[str, torch.Tensor]] = None
+        self._graph = self._graph_in = self._graph_out = None
 
-    # ------------------------------------------------------------------
-    def process_packed(
-        self, lines: torch.Tensor, line_len: torch.Tensor,
-        n_valid: Optional[int] = None, rate: bool = True,
-    ) -> Dict[str, torch.Tensor]:
+    def process_packed(self, lines: torch.Tensor, line_len: torch.Tensor,
+                       n_valid: Optional[int] = None, rate: bool = True) -> dict:
         """lines [B, max_len] u8 + lengths on self.device → result tensors.
 
         Returns event_id [B], anomaly [B] (bool), scores [B] (f32, 0 when
@@ -179,232 +113,137 @@ class GpuPipeline:
         ``n_valid`` and ``rate`` concern the event-rate stage alone, the one
         stage with stream state: only the first n_valid rows (default: all)
         enter its windows, and ``rate=False`` skips it, so the call neither
-        moves that state nor reports rate alerts (a re-score of old lines)."""
+        moves that state nor reports rate alerts (its keys are None). The
+        first ``train_lines`` rows of the stream train; the stream position
+        ``seen_lines`` moves only here and in a graph replay."""
         B = lines.shape[0]
-        if B == 0:
-            return {
-                "event_id": torch.zeros(0, dtype=torch.int32, device=lines.device),
-                "anomaly": torch.zeros(0, dtype=torch.bool, device=lines.device),
-                "scores": torch.zeros(0, dtype=torch.float32, device=lines.device),
-                "nv_unseen": None,
-                "combo_unseen": None,
-                "match": None,
-                **(dict.fromkeys(self._RATE_KEYS)
-                   if self.event_rate is not None else {}),
-                **self._empty_range_out(lines.device),
-            }
-        # roctx-visible stage ranges (torch.cuda.nvtx maps to rocTracer
-        # markers on ROCm — SURVEY.md §5.1 tracing requirement)
-        _rng = torch.cuda.nvtx.range if lines.is_cuda else None
-        if _rng:
-            torch.cuda.nvtx.range_push("dmx::parse")
-        match = self.matcher.match_packed(lines, line_len)
-        if _rng:
-            torch.cuda.nvtx.range_pop()
-
-        n_train_left = max(0, self.config.train_lines - self.seen_lines)
-        train_upto = min(B, n_train_left)
+        train_upto = min(B, max(0, self.config.train_lines - self.seen_lines))
+        out = self._run(lines, line_len, train_upto, n_valid, rate,
+                        self.config.score_threshold)
         self.seen_lines += B
+        return out
 
-        # without event_rate the result holds exactly the keys it always
-        # held; with it the four keys are there, None when the stage is
-        # skipped (read them with .get())
-        rate_out = (dict.fromkeys(self._RATE_KEYS)
-                    if self.event_rate is not None else {})
-        if self.event_rate is not None and rate:
-            if _rng:
-                torch.cuda.nvtx.range_push("dmx::event_rate")
-            rate_out = self.event_rate.step(match["event_id"], n_valid, train_upto)
-            if _rng:
-                torch.cuda.nvtx.range_pop()
+    def rescore(self, lines: torch.Tensor, lens: torch.Tensor,
+                threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """Judge old lines as the detect phase would, with ``threshold`` in
+        place of the configured one if given: nothing trains, the event-rate
+        stage is skipped, the stream position stays."""
+        return self._run(lines, lens, 0, None, False, float(
+            self.config.score_threshold if threshold is None else threshold))
 
-        # value ranges: rows below train_upto move lo / hi / n, every row is
-        # judged against the state after them; the two keys exist only with
-        # ranges configured
-        range_out: Dict[str, torch.Tensor] = {}
-        if self.value_ranges is not None:
-            if _rng:
-                torch.cuda.nvtx.range_push("dmx::value_range")
-            code, value = self.value_ranges.step(lines, match, train_upto)
-            range_out = {"range_code": code, "range_value": value}
-            if _rng:
-                torch.cuda.nvtx.range_pop()
-
-        nv_unseen = None  # here [B, W + C]; split into its two views below
-        W = self.specs.shape[0]
-        if _rng:
-            torch.cuda.nvtx.range_push("dmx::new_value")
-        if self.hashsets is not None:
-            if self.n_combos:
-                hashes = ops.watch_combo_hashes(
-                    lines, match, self.specs, self.members, self.combo_off,
-                    self.config.lowercase)
-            else:
-                hashes = ops.watch_hashes(lines, match, self.specs, self.config.lowercase)
-            if train_upto > 0:
-                self.hashsets.insert(hashes[:train_upto])
-            if train_upto == 0:
-                # steady state: probe output IS the result (a zeros +
-                # full-copy here cost 2 kernel launches per batch)
-                nv_unseen = self.hashsets.probe(hashes)
-            elif train_upto < B:
-                unseen_tail = self.hashsets.probe(hashes[train_upto:])
-                nv_unseen = torch.zeros(
-                    (B, W + self.n_combos), dtype=torch.int32, device=lines.device
-                )
-                nv_unseen[train_upto:] = unseen_tail
-            else:
-                nv_unseen = torch.zeros(
-                    (B, W + self.n_combos), dtype=torch.int32, device=lines.device
-                )
-
-        if _rng:
-            torch.cuda.nvtx.range_pop()
-
-        scores = torch.zeros(B, dtype=torch.float32, device=lines.device)
-        if _rng:
-            torch.cuda.nvtx.range_push("dmx::transformer")
-        if self.model is not None:
-            # content span comes straight from the match kernel
-            # (span_start/span_end outputs — the former gather/where
-            # chain here was ~6 kernel launches per batch, profiles/r10)
-            if self.embedding_stats is not None:
-                scores = self._embedding_scores(
-                    lines, match["span_start"], match["span_end"], train_upto)
-            else:
-                scores = self.model.score_spans(
-                    lines, match["span_start"], match["span_end"])
-        if _rng:
-            torch.cuda.nvtx.range_pop()
-
-        anomaly = scores > self.config.score_threshold
-        combo_unseen = None
-        if nv_unseen is not None:
-            # one reduction over watch and combination columns alike
-            anomaly = anomaly | (nv_unseen.sum(dim=1) > 0)
-            if self.n_combos:
-                combo_unseen = nv_unseen[:, W:]
-                nv_unseen = nv_unseen[:, :W] if W else None
-        if rate_out.get("rate_hits") is not None:
-            # non-zero only on a boundary line outside the training phase
-            anomaly = anomaly | (rate_out["rate_hits"] > 0)
-        if range_out:
-            anomaly = anomaly | (range_out["range_code"] != 0).any(dim=1)
-        return {
-            "event_id": match["event_id"],
-            "anomaly": anomaly,
-            "scores": scores,
-            "nv_unseen": nv_unseen,
-            "combo_unseen": combo_unseen,
+    def _run(self, lines, line_len, train_upto: int, n_valid: Optional[int],
+             rate: bool, threshold: float) -> Dict[str, torch.Tensor]:
+        """Parse, every stage, OR of the flags. Reads and writes neither
+        seen_lines nor config.score_threshold."""
+        B, dev = lines.shape[0], lines.device
+        match = (marked("dmx::parse", dev, self.matcher.match_packed, lines, line_len)
+                 if B else None)
+        out = {
+            "event_id": (match["event_id"] if B
+                         else torch.zeros(0, dtype=torch.int32, device=dev)),
+            "anomaly": None,
+            "scores": torch.zeros(B, dtype=torch.float32, device=dev),
+            "nv_unseen": None, "combo_unseen": None,
             "match": match,
-            **rate_out,
-            **range_out,
         }
-
-    def _empty_range_out(self, device) -> Dict[str, torch.Tensor]:
-        """The value-range keys of an empty batch ({} without ranges)."""
-        if self.value_ranges is None:
-            return {}
-        R = self.value_ranges.R
-        return {
-            "range_code": torch.zeros((0, R), dtype=torch.int32, device=device),
-            "range_value": torch.zeros((0, R), dtype=torch.float64, device=device),
-        }
-
-    def _embedding_scores(
-        self, lines: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
-        train_upto: int,
-    ) -> torch.Tensor:
-        """score_mode "embedding": rows below train_upto update the moments
-        and score 0, the rest score their distance. A batch that straddles
-        the boundary takes a second launch on its tail; steady state is one
-        distance-only launch."""
-        stats = self.embedding_stats
-        B = lines.shape[0]
-        if train_upto > 0:
-            stats.update(self.model.embed_spans(
-                lines[:train_upto], start[:train_upto], end[:train_upto]))
-        if train_upto == B or stats.n == 0:  # nothing fitted: no distance
-            return torch.zeros(B, dtype=torch.float32, device=lines.device)
-        if train_upto == 0:
-            return self.model.embed_distance_spans(
-                lines, start, end, stats.mu, stats.inv_var)
-        scores = torch.zeros(B, dtype=torch.float32, device=lines.device)
-        scores[train_upto:] = self.model.embed_distance_spans(
-            lines[train_upto:], start[train_upto:], end[train_upto:],
-            stats.mu, stats.inv_var)
-        return scores
+        # a stage's keys are there whenever it is configured: those of an
+        # empty batch for B == 0, None when it is skipped (read with .get())
+        for s in self.stages:
+            skip = B == 0 or (s.windowed and not rate)
+            out.update(s.empty(dev) if skip else marked(
+                "dmx::" + s.name, dev, s.run, lines, match, train_upto, n_valid))
+        anomaly = out["scores"] > threshold
+        for s in self.stages if B else ():
+            flag = s.flags(out)
+            if flag is not None:
+                anomaly = anomaly | flag
+        out["anomaly"] = anomaly
+        return out
 
     def process_lines(self, raw_lines: Sequence[bytes]) -> Dict[str, torch.Tensor]:
         lines, lens = ops.pack_lines(raw_lines, self.config.max_len, device=self.device)
         return self.process_packed(lines, lens)
 
-    # ------------------------------------------------------------------
+    # state: seen_lines plus each stage's, under its checkpoint key. A key with
+    # no configured stage is ignored; a stage with no key keeps its start state.
+    def state_dict(self) -> Dict[str, Any]:
+        state: Dict[str, Any] = {"seen_lines": self.seen_lines}
+        for s in self.stages:
+            state.update(s.state_dict())
+        return state
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self.seen_lines = int(state.get("seen_lines", 0))
+        for s in self.stages:
+            s.load_state_dict(state)
+
+    def dist_sync(self, group=None) -> None:
+        """COLLECTIVE merge of the data-parallel state of every stage that
+        has one: hash sets by union, value ranges by MIN / MAX / SUM."""
+        import torch.distributed as tdist
+        if not tdist.is_initialized() or tdist.get_world_size(group) <= 1:
+            return
+        for s in self.stages:
+            s.dist_sync(group)
+
     # hipGraph capture (HIP graphs for the launch-bound steady state —
     # SURVEY.md build mandate). Valid only AFTER the training phase: the
     # captured graph replays the detect-only path at fixed batch size.
-    # ------------------------------------------------------------------
+    @property
+    def graph_enabled(self) -> bool:
+        return self._graph is not None
+
     def enable_graph(self, batch_size: int) -> bool:
         if self.device.type != "cuda":
             return False
         if self.seen_lines < self.config.train_lines:
             raise RuntimeError("enable_graph() requires the training phase done")
-        B = batch_size
         static_lines = torch.zeros(
-            (B, self.config.max_len), dtype=torch.uint8, device=self.device
-        )
-        static_lens = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            (batch_size, self.config.max_len), dtype=torch.uint8, device=self.device)
+        static_lens = torch.zeros((batch_size,), dtype=torch.int32, device=self.device)
         # warm up allocator/kernels on the same shapes, then capture. The
         # event-rate stage reads its row count from a device word: 0 makes
         # the warm-ups rewrite its state with the values it holds, and the
         # captured launches read whatever the word holds at replay.
+        args = (static_lines, static_lens, 0, 0, True, self.config.score_threshold)
         for _ in range(2):
-            self.process_packed(static_lines, static_lens, n_valid=0)
-            self.seen_lines -= B  # warmups must not advance stream state
+            self._run(*args)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self.process_packed(static_lines, static_lens, n_valid=0)
-        self.seen_lines -= B
-        self._graph = graph
-        self._graph_in = (static_lines, static_lens)
-        self._graph_out = out
+            out = self._run(*args)
+        self._graph, self._graph_in, self._graph_out = graph, args[:2], out
         return True
 
-    def process_packed_graph(
-        self, lines: torch.Tensor, lens: torch.Tensor
-    ) -> Dict[str, torch.Tensor]:
-        """Replay the captured graph on a new batch (same B, max_len)."""
-        assert self._graph is not None, "call enable_graph() first"
-        sl, sn = self._graph_in
-        sl.copy_(lines, non_blocking=True)
-        sn.copy_(lens, non_blocking=True)
-        if self.event_rate is not None:
-            self.event_rate.set_n_valid(lines.shape[0])
-        self._graph.replay()
-        self.seen_lines += lines.shape[0]
-        return self._graph_out
-
-    def process_packed_graph_partial(
-        self, lines: torch.Tensor, lens: torch.Tensor
-    ) -> Dict[str, torch.Tensor]:
-        """Replay on a batch SMALLER than the captured size: pad rows get
-        len 0 (their kernels no-op on the span but the transformer still
-        runs them — acceptable when partial batches are rare stream
-        edges). Outputs are sliced back to the true batch size."""
+    def _replay(self, lines: torch.Tensor, lens: torch.Tensor) -> int:
+        """Copy B <= captured rows in (pad rows get len 0), replay."""
         assert self._graph is not None, "call enable_graph() first"
         sl, sn = self._graph_in
         B = lines.shape[0]
         assert B <= sl.shape[0]
-        sl[:B].copy_(lines, non_blocking=True)
-        sn[:B].copy_(lens, non_blocking=True)
-        if B < sn.shape[0]:
+        full = B == sl.shape[0]
+        (sl if full else sl[:B]).copy_(lines, non_blocking=True)
+        (sn if full else sn[:B]).copy_(lens, non_blocking=True)
+        if not full:
             sn[B:].zero_()
-        if self.event_rate is not None:
-            # pad rows parse as unparsed lines; they must not be counted
-            self.event_rate.set_n_valid(B)
+        for s in self.stages:
+            s.before_replay(B)
         self._graph.replay()
         self.seen_lines += B
+        return B
+
+    def process_packed_graph(self, lines: torch.Tensor, lens: torch.Tensor) -> dict:
+        """Replay the captured graph on a new batch (same B, max_len)."""
+        self._replay(lines, lens)
+        return self._graph_out
+
+    def process_packed_graph_partial(self, lines: torch.Tensor, lens: torch.Tensor) -> dict:
+        """Replay on a batch SMALLER than the captured size: pad rows get
+        len 0 (their kernels no-op on the span but the transformer still
+        runs them — acceptable when partial batches are rare stream
+        edges). Outputs are sliced back to the true batch size."""
+        B = self._replay(lines, lens)
+        whole = {k for s in self.stages for k in s.per_slot_keys}
 
         def cut(v):
             if torch.is_tensor(v):
@@ -413,5 +252,4 @@ class GpuPipeline:
                 return {k: cut(x) for k, x in v.items()}
             return v
 
-        return {k: (v if k in self._PER_SLOT_KEYS else cut(v))
-                for k, v in self._graph_out.items()}
+        return {k: (v if k in whole else cut(v)) for k, v in self._graph_out.items()}
