@@ -89,8 +89,12 @@ def match_template(content: str, segments: List[str]) -> Optional[List[str]]:
 
     Segments must appear in order; the first segment anchors at position 0
     when non-empty, the last must end the string when non-empty. Returns
-    the wildcard captures, or None. This exact algorithm is mirrored by
-    the HIP kernel in ops/csrc/template_match.hip.
+    the wildcard captures, or None. The HIP kernel in
+    ops/csrc/template_match.hip runs the same algorithm on bytes: its
+    offsets are byte offsets and its ``lowercase`` folds A-Z only. This
+    function serves ``str`` log lines (characters, ``str.lower()``), so the
+    two agree on ASCII content only; ``ops.TemplateMatcher._match_cpu`` is
+    the byte-exact Python mirror of the kernel.
     """
     captures: List[str] = []
     pos = 0

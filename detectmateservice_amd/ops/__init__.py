@@ -230,20 +230,21 @@ class TemplateMatcher:
             )
             out = {"event_id": ev, "fmt_caps": fc, "n_fmt_caps": nfc,
                    "caps": caps, "n_caps": ncaps}
-            self._add_spans(out, line_len)
+            self._add_spans(out, line_len, lines.shape[1])
             return out
         out = self._match_cpu(lines, line_len)
-        self._add_spans(out, line_len)
+        self._add_spans(out, line_len, lines.shape[1])
         return out
 
     @staticmethod
-    def _add_spans(match: dict, line_len: torch.Tensor) -> None:
-        """CPU-path twin of the kernel's span outputs: content span =
-        last header capture when the format matched, else [0, len)."""
+    def _add_spans(match: dict, line_len: torch.Tensor, max_len: int) -> None:
+        """CPU-path twin of the kernel's span outputs: content span = last
+        written header capture when the format matched, else [0, len) with
+        len = min(line_len, max_len) as the kernel cuts it."""
         nfc = match["n_fmt_caps"].long()
         has_hdr = nfc > 0
-        last = (nfc - 1).clamp(min=0)
         fc = match["fmt_caps"]
+        last = (nfc.clamp(max=fc.shape[1]) - 1).clamp(min=0)
         start = torch.where(
             has_hdr,
             fc.gather(1, last.view(-1, 1, 1).expand(-1, 1, 2))[:, 0, 0].long(),
@@ -252,16 +253,19 @@ class TemplateMatcher:
         end = torch.where(
             has_hdr,
             fc.gather(1, last.view(-1, 1, 1).expand(-1, 1, 2))[:, 0, 1].long(),
-            line_len.long(),
+            line_len.long().clamp(max=int(max_len)),
         )
         match["span_start"] = start.int()
         match["span_end"] = end.int()
 
-    # -- CPU reference (same algorithm, used for CI + kernel parity tests) --
+    # -- pure-Python mirror of the kernel (runs when the extension is absent) --
     def _match_cpu(self, lines: torch.Tensor, line_len: torch.Tensor):
-        from ..library.parsers.template_matcher import match_template
-
-        B = lines.shape[0]
+        """The kernel's match on the CPU, in bytes like the kernel and the
+        C++ twin: a line is its first min(line_len, max_len) bytes, every
+        offset is a byte offset, and ``lowercase`` folds A-Z only, and only
+        for the content match (the format match never folds). No byte of the
+        line is decoded, so lines that are not UTF-8 match the same way."""
+        B, max_len = lines.shape[0], lines.shape[1]
         ev = torch.full((B,), -1, dtype=torch.int32)
         fc = torch.zeros((B, self.max_fmt_caps, 2), dtype=torch.int32)
         nfc = torch.zeros((B,), dtype=torch.int32)
@@ -270,28 +274,28 @@ class TemplateMatcher:
 
         fmt_segs = None
         if self.log_format:
-            import re
-
-            fmt_segs = re.sub(
+            fmt_segs = [s.encode("utf-8") for s in re.sub(
                 r"<[A-Za-z_][A-Za-z0-9_]*>", "<*>", self.log_format
-            ).split("<*>")
-        tpl_segs = [t.split("<*>") for t in self.templates]
+            ).split("<*>")]
+        tpl_segs = [[s.encode("utf-8") for s in t.split("<*>")]
+                    for t in self.templates]
 
+        rows = lines.numpy()
+        lens = line_len.tolist()
         for i in range(B):
-            raw = bytes(lines[i, : int(line_len[i])].numpy().tobytes())
-            text = raw.decode("utf-8", errors="replace")
-            start, end = 0, len(text)
+            raw = rows[i, : min(max(int(lens[i]), 0), max_len)].tobytes()
+            start, end = 0, len(raw)
             if fmt_segs:
-                spans = _span_match(text, 0, len(text), fmt_segs)
+                spans = _span_match(raw, 0, len(raw), fmt_segs)
                 if spans is not None:
                     nfc[i] = len(spans)
                     for j, (a, b) in enumerate(spans[: self.max_fmt_caps]):
                         fc[i, j, 0], fc[i, j, 1] = a, b
                     if spans:
-                        start, end = spans[-1]
-            cmp_text = text.lower() if self.lowercase else text
+                        start, end = spans[: self.max_fmt_caps][-1]
+            cmp_raw = raw.translate(_ASCII_FOLD) if self.lowercase else raw
             for t, segs in enumerate(tpl_segs):
-                spans = _span_match(cmp_text, start, end, segs)
+                spans = _span_match(cmp_raw, start, end, segs)
                 if spans is not None:
                     ev[i] = t + 1
                     ncaps[i] = len(spans)
@@ -302,14 +306,20 @@ class TemplateMatcher:
                 "caps": caps, "n_caps": ncaps}
 
 
-def _span_match(text: str, start: int, end: int, segments: List[str]):
-    """match_template returning (start, end) spans instead of strings —
-    the exact algorithm of template_match.hip::match_segments."""
+#: bytes.translate table of the kernel's fold: A-Z -> a-z, every other byte
+#: (0x80 - 0xff included) unchanged
+_ASCII_FOLD = bytes(c + 32 if 65 <= c <= 90 else c for c in range(256))
+
+
+def _span_match(text: bytes, start: int, end: int, segments: List[bytes]):
+    """The algorithm of template_match.hip::match_segments on ``bytes``:
+    greedy-anchored, byte offsets, (start, end) spans or None. The caller
+    folds ``text``; the segments are compared as they are."""
     pos = start
     spans: List[Tuple[int, int]] = []
     n = len(segments)
     for i, seg in enumerate(segments):
-        if seg == "":
+        if len(seg) == 0:
             if i == n - 1:
                 spans.append((pos, end))
                 return spans

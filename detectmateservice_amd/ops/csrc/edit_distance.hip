@@ -26,8 +26,12 @@ void dmx_edit_distance(
   if (pair >= (long)Na * Nb) return;
   const int ia = (int)(pair / Nb);
   const int ib = (int)(pair % Nb);
-  const int m = min(a_len[ia], ED_MAX_LEN);  // rows (string a)
-  const int n = min(b_len[ib], ED_MAX_LEN);  // cols (string b)
+  // The length words live on the device, so the bindings cannot check them:
+  // clamp to [0, min(max_len, ED_MAX_LEN)], the bytes the row and the LDS
+  // carve hold (kernels.h).
+  const int cap = min(max_len, ED_MAX_LEN);
+  const int m = min(max(a_len[ia], 0), cap);  // rows (string a)
+  const int n = min(max(b_len[ib], 0), cap);  // cols (string b)
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // per-wave carve: a[256] + b[256] + 3 diagonal arrays of (ED_MAX_LEN+1) u16

@@ -108,7 +108,9 @@ void dmx_hashset_insert(
     if (prev == EMPTY_KEY || prev == h) return;
     slot = (slot + 1) & (capacity - 1);
   }
-  // table full: drop (host sizes capacity with 4x headroom and monitors fill)
+  // table full: the value is dropped. Nothing watches the fill; the capacity
+  // comes from the configuration (hashset_capacity), sized for >= 4x the
+  // expected cardinality. A dropped value keeps probing as unseen.
 }
 
 extern "C" __global__ __launch_bounds__(256)

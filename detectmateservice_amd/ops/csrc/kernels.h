@@ -221,7 +221,9 @@ void dmx_launch_value_range(ParsedBatch batch, const int32_t* specs, int R,
                             int64_t* n, int train_upto, int32_t* range_code,
                             double* range_value, hipStream_t stream);
 
-// edit_distance.hip
+// edit_distance.hip: dist [Na, Nb] int32. A and B are [N, max_len] rows with
+// max_len <= ED_MAX_LEN; the kernel clamps every word of a_len and b_len to
+// [0, min(max_len, ED_MAX_LEN)], so a length word never reaches past its row.
 void dmx_launch_edit_distance(const uint8_t* A, const int32_t* a_len, int Na,
                               const uint8_t* B, const int32_t* b_len, int Nb,
                               int max_len, int32_t* dist, hipStream_t stream);

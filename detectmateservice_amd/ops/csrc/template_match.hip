@@ -5,9 +5,11 @@
 // (reference capability: parsers.template_matcher) and for
 // the Levenshtein/template native ext the reference library family uses
 // (detectmateperformance). The matching algorithm is the
-// exact greedy-anchored wildcard match of
-// detectmateservice_amd/library/parsers/template_matcher.py::match_template
-// (the Python implementation is the semantic reference; parity is tested).
+// greedy-anchored wildcard match of
+// detectmateservice_amd/library/parsers/template_matcher.py::match_template,
+// run on bytes: offsets are byte offsets and `lower` folds A-Z only, for the
+// content match only. docs/kernels.md, "dmx_template_match", states the
+// contract; tests/test_template_match_gpu.py holds the kernel to it.
 //
 // Layout: lines live in a padded SoA byte buffer [B, max_len] (decoded from
 // protobuf frames once per batch, SURVEY.md §2.4 "GPU-resident columnar
