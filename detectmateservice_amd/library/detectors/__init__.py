@@ -36,3 +36,6 @@ __all__ += ["SklearnDetector", "SklearnDetectorConfig",
 from .value_range import ValueRangeDetector, ValueRangeDetectorConfig
 
 __all__ += ["ValueRangeDetector", "ValueRangeDetectorConfig"]
+from .event_sequence import EventSequenceDetector, EventSequenceDetectorConfig
+
+__all__ += ["EventSequenceDetector", "EventSequenceDetectorConfig"]

@@ -48,6 +48,11 @@ class FusedPipelineDetectorConfig(CoreConfig):
     #: The line that completes a window alerts when an event's count in it
     #: is z_threshold sigmas off its EWMA baseline. None = off.
     event_rate: Optional[Dict[str, Any]] = None
+    #: event sequences: {length, key, max_keys, capacity}. A line alerts
+    #: when the n-gram of event ids it completes in the history of its key
+    #: (a field written like a watch, e.g. the session id; no key = the
+    #: whole stream) never occurred in the data_use_training rows. None = off.
+    event_sequence: Optional[Dict[str, Any]] = None
     #: numeric value ranges: [{kind, pos, event, name, slack, non_numeric,
     #: min, max}], the first three as in watches. The field is read as a
     #: decimal number; its smallest and largest value over the
@@ -100,6 +105,8 @@ class FusedPipelineDetector(CoreComponent):
                 train_lines=cfg.data_use_training,
                 event_rate=(dict(cfg.event_rate)
                             if cfg.event_rate is not None else None),
+                event_sequence=(dict(cfg.event_sequence)
+                                if cfg.event_sequence is not None else None),
                 ranges=[dict(r) for r in (cfg.ranges or [])],
                 seed=cfg.seed,
             ),
@@ -137,8 +144,9 @@ class FusedPipelineDetector(CoreComponent):
         line buffer — post-hoc analysis with a NEW threshold (or model
         state) at HBM bandwidth, the config-5 use case. Returns summary
         counts (the alert path stays with the live stream). The event-rate
-        stage is skipped: old lines belong to no window of the live stream,
-        so its state stays as it is and no rate alert is counted."""
+        and event-sequence stages are skipped: old lines belong to no window
+        and no history of the live stream, so their state stays as it is and
+        none of their alerts is counted."""
         if self.line_buffer is None:
             return {"rescored": 0, "reason": "line buffer disabled"}
         lines, lens = self.line_buffer.window(lines_back)

@@ -1020,3 +1020,213 @@ class ValueRangeState:
         self.lo.copy_(torch.minimum(self.lo, lo.to(self.lo)))
         self.hi.copy_(torch.maximum(self.hi, hi.to(self.hi)))
         self.n.add_(n.to(self.n))
+
+
+# ---------------------------------------------------------------------------
+# detector: event sequences (docs/kernels.md, "Event sequences" is the
+# definition; event_sequence.hip and event_sequence_step_cpu below implement it)
+# ---------------------------------------------------------------------------
+
+#: kernels.h limits, repeated here so that a CPU-only install can refuse a
+#: configuration the GPU could not run (tests compare them to the extension's)
+SEQ_MAX_LEN = 4
+SEQ_MAX_KEYS = 1 << 24
+SEQ_MAX_EVENTS = 65535
+
+#: the keys of `event_sequence:` and their defaults (capacity None = the
+#: pipeline's hashset_capacity)
+EVENT_SEQUENCE_DEFAULTS = {
+    "length": 3,
+    "key": None,
+    "max_keys": 1 << 16,
+    "capacity": None,
+}
+_SEQ_KEY_KEYS = ("kind", "pos", "event", "name")
+
+
+def _check_event_sequence_params(length, max_keys, n_templates) -> None:
+    if not 2 <= int(length) <= SEQ_MAX_LEN:
+        raise ValueError(
+            f"length must be within 2 .. SEQ_MAX_LEN = {SEQ_MAX_LEN}, got {length}")
+    K = int(max_keys)
+    if not (1 <= K <= SEQ_MAX_KEYS and K & (K - 1) == 0):
+        raise ValueError(
+            f"max_keys must be a power of two within 1 .. SEQ_MAX_KEYS = "
+            f"{SEQ_MAX_KEYS}, got {max_keys}")
+    if not 0 <= int(n_templates) <= SEQ_MAX_EVENTS:
+        raise ValueError(
+            f"event_sequence supports at most SEQ_MAX_EVENTS = {SEQ_MAX_EVENTS} "
+            f"templates (a symbol is 16 bits), got {n_templates}")
+
+
+def sequence_key_row(key: Optional[dict]) -> Tuple[int, int, int]:
+    """The `key:` entry of event_sequence -> (kind, event, pos) of its watch
+    spec, or (-1, -1, 0) for no key."""
+    if key is None:
+        return (-1, -1, 0)
+    unknown = set(key) - set(_SEQ_KEY_KEYS)
+    if unknown:
+        raise ValueError(
+            f"event_sequence key: unknown key(s) {sorted(unknown)}; valid keys: "
+            f"{sorted(_SEQ_KEY_KEYS)}")
+    if "pos" not in key:
+        raise ValueError(f"event_sequence key has no 'pos': {dict(key)!r}")
+    if key.get("kind", "variable") not in ("variable", "header"):
+        raise ValueError(
+            f"event_sequence key: 'kind' must be 'variable' or 'header', "
+            f"got {key['kind']!r}")
+    kind, event, pos, _ = watch_spec_row(key)
+    if pos < 0:
+        raise ValueError(f"event_sequence key: 'pos' must be >= 0, got {pos}")
+    return (kind, event, pos)
+
+
+def sequence_bucket(kh: int, max_keys: int) -> int:
+    """Bucket of key hash ``kh`` (unsigned or int64 view) among max_keys."""
+    kh &= _U64
+    return ((kh >> 32) ^ kh) & (int(max_keys) - 1)
+
+
+def gram_hash(gram: int) -> int:
+    """Hash of a gram word: its 8 bytes, low byte first, folded FNV-1a style
+    and forced odd (unsigned)."""
+    h = FNV_OFFSET
+    for b in range(8):
+        h = ((h ^ ((gram >> (8 * b)) & 0xFF)) * FNV_PRIME) & _U64
+    return h | 1
+
+
+def event_sequence_step_cpu(lines, match: dict, key_row, lower: bool, n_valid,
+                            n_templates: int, seq_key, seq_hist, length: int):
+    """CPU mirror of ``_dmx_C.event_sequence_step``: the sequential loop of
+    the definition over the member rows, in row order. seq_key and seq_hist
+    (int64 [K]) are updated in place; returns (seq_gram int64 [B], gram_hash
+    int64 [B, 1]). Plain Python integers throughout."""
+    B, max_len = int(lines.shape[0]), int(lines.shape[1])
+    K, n = int(seq_key.shape[0]), int(length)
+    _check_event_sequence_params(n, K, n_templates)
+    if tuple(seq_hist.shape) != (K,):
+        raise ValueError(f"seq_hist must hold K = {K} elements, got {list(seq_hist.shape)}")
+    kind, event, pos = key_row
+    grams = torch.zeros(B, dtype=torch.int64)
+    hashes = torch.zeros((B, 1), dtype=torch.int64)
+    if B == 0:
+        return grams, hashes
+    nv = min(max(int(n_valid), 0), B)
+    ev = match["event_id"].tolist()
+    parsed = [t.tolist() for t in _parsed_args(lines, match)[1:]] if kind >= 0 else None
+    rows = lines.numpy()
+    gram_mask = (1 << (16 * n)) - 1
+    hist_mask = (1 << (16 * (n - 1))) - 1
+    for i in range(nv):
+        if not 1 <= ev[i] <= int(n_templates):
+            continue
+        if kind >= 0:
+            span = _field_span(parsed, max_len, (kind, event, pos, 0), i)
+            if span is None:
+                continue
+            kh = fnv1a64(rows[i, span[0]:span[1]].tobytes(), lower)
+        else:
+            kh = 1
+        b = sequence_bucket(kh, K)
+        if int(seq_key[b]) & _U64 != kh:  # take the bucket over
+            seq_key[b] = _as_i64(kh)
+            seq_hist[b] = 0
+        gram = (((int(seq_hist[b]) & _U64) << 16) | ev[i]) & gram_mask
+        seq_hist[b] = _as_i64(gram & hist_mask)
+        grams[i] = _as_i64(gram)
+        hashes[i, 0] = _as_i64(gram_hash(gram))
+    return grams, hashes
+
+
+def event_sequence_step(lines, match: dict, key_row, lower: bool, n_valid,
+                        n_templates: int, seq_key, seq_hist, length: int):
+    """One batch of the event-sequence stage on lines' device."""
+    if lines.is_cuda:
+        gram, hashes = _require_ext().event_sequence_step(
+            *_parsed_args(lines, match), int(key_row[0]), int(key_row[1]),
+            int(key_row[2]), bool(lower), n_valid, int(n_templates), seq_key,
+            seq_hist, int(length))
+        return gram, hashes
+    return event_sequence_step_cpu(lines, match, key_row, lower, n_valid,
+                                   n_templates, seq_key, seq_hist, length)
+
+
+def decode_gram(gram: int, length: int) -> List[int]:
+    """The ``length`` symbols of a gram word, oldest first, 0 = pad."""
+    gram &= _U64
+    return [(gram >> (16 * j)) & 0xFFFF for j in range(int(length) - 1, -1, -1)]
+
+
+def sequence_text(symbols: Sequence[int], key_name: Optional[str] = None) -> str:
+    """Alert wording of an unknown gram: "unknown event sequence: ^ > 3 > 7
+    (per ses)", ^ for a pad."""
+    text = "unknown event sequence: " + " > ".join(
+        "^" if s == 0 else str(s) for s in symbols)
+    return text + (f" (per {key_name})" if key_name else "")
+
+
+class EventSequenceState:
+    """Per-key histories of the event-sequence stage, resident on ``device``:
+    ``seq_key`` (the key hash that owns each of the K = max_keys buckets, 0 =
+    nobody) and ``seq_hist`` (its last length - 1 event ids, 16 bits each),
+    both int64 [K]. ``step`` advances them by one batch without a host read,
+    so it can be captured into a hipGraph; restoring a checkpoint writes into
+    the same tensors, which a captured graph keeps reading."""
+
+    _STATE = ("seq_key", "seq_hist")
+
+    def __init__(self, n_templates: int, length: int = 3, max_keys: int = 1 << 16,
+                 key: Optional[dict] = None, lowercase: bool = False,
+                 device="cpu") -> None:
+        _check_event_sequence_params(length, max_keys, n_templates)
+        self.n_templates = int(n_templates)
+        self.length = int(length)
+        self.max_keys = int(max_keys)
+        self.key_row = sequence_key_row(key)
+        self.key_name = (key or {}).get("name")
+        self.lowercase = bool(lowercase)
+        self.device = torch.device(device)
+        self.seq_key = torch.zeros(self.max_keys, dtype=torch.int64, device=self.device)
+        self.seq_hist = torch.zeros(self.max_keys, dtype=torch.int64, device=self.device)
+        # the row count handed to the kernels: a device word, rewritten only
+        # when the count changes (a captured graph reads it at replay)
+        self.n_valid = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._n_valid_host = 0
+
+    def set_n_valid(self, n: int) -> None:
+        if int(n) != self._n_valid_host:
+            self.n_valid.fill_(int(n))
+            self._n_valid_host = int(n)
+
+    def step(self, lines: torch.Tensor, match: dict, n_valid: Optional[int] = None):
+        """(seq_gram int64 [B], gram_hash int64 [B, 1]) of one parsed batch;
+        the first ``n_valid`` rows (default: all) move the histories.
+        ``n_valid=None`` inside a graph capture would record the write;
+        callers that capture set it first with set_n_valid()."""
+        self.set_n_valid(lines.shape[0] if n_valid is None else n_valid)
+        return event_sequence_step(
+            lines, match, self.key_row, self.lowercase, self.n_valid,
+            self.n_templates, self.seq_key, self.seq_hist, self.length)
+
+    def state_dict(self) -> dict:
+        state = {k: getattr(self, k).detach().cpu().clone() for k in self._STATE}
+        state["length"] = self.length
+        state["max_keys"] = self.max_keys
+        return state
+
+    def load_state_dict(self, state: dict) -> None:
+        for k in ("length", "max_keys"):
+            if int(state[k]) != getattr(self, k):
+                raise ValueError(
+                    f"event-sequence checkpoint was taken with {k} = {int(state[k])} "
+                    f"but this instance is configured for {getattr(self, k)} "
+                    "(its histories would mean other grams)")
+        for k in self._STATE:
+            if tuple(state[k].shape) != (self.max_keys,):
+                raise ValueError(
+                    f"event-sequence checkpoint holds {k} {list(state[k].shape)} but "
+                    f"this instance is configured for max_keys = {self.max_keys}")
+        for k in self._STATE:
+            mine = getattr(self, k)
+            mine.copy_(state[k].to(mine.dtype))

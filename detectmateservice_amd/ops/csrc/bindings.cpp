@@ -11,6 +11,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <c10/hip/HIPException.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <initializer_list>
 
@@ -787,6 +788,80 @@ std::vector<torch::Tensor> value_range_step(
   return {range_code, range_value};
 }
 
+// ---- event sequences (docs/kernels.md, "Event sequences") ----------------------
+
+py::dict event_sequence_limits() {
+  py::dict d;
+  d["max_len"] = SEQ_MAX_LEN;
+  d["max_keys"] = SEQ_MAX_KEYS;
+  d["max_events"] = SEQ_MAX_EVENTS;
+  return d;
+}
+
+// One batch of the event-sequence stage. seq_key and seq_hist are updated in
+// place; returns (seq_gram int64 [B], gram_hash int64 [B, 1]). The key field
+// is (key_kind, key_event, key_pos) of a watch spec, key_kind < 0 = no key.
+// The sort's scratch comes from torch's allocator, sized by rocPRIM's query
+// call, which launches nothing. Nothing here reads a tensor's values.
+std::vector<torch::Tensor> event_sequence_step(
+    torch::Tensor lines, torch::Tensor event_id, torch::Tensor caps,
+    torch::Tensor n_caps, torch::Tensor fmt_caps, torch::Tensor n_fmt_caps,
+    int64_t key_kind, int64_t key_event, int64_t key_pos, bool lower,
+    torch::Tensor n_valid, int64_t n_templates, torch::Tensor seq_key,
+    torch::Tensor seq_hist, int64_t length) {
+  const ParsedBatch batch =
+      check_parsed_batch(lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps);
+  const auto B = lines.size(0);
+  TORCH_CHECK(key_kind >= -1 && key_kind <= 1,
+              "key_kind must be -1 (no key), 0 (variable) or 1 (header), got ",
+              key_kind);
+  TORCH_CHECK(key_kind < 0 || (key_pos >= 0 && key_pos <= INT32_MAX),
+              "key_pos must be within 0 .. 2^31 - 1, got ", key_pos);
+  TORCH_CHECK(key_event >= -1 && key_event <= INT32_MAX,
+              "key_event must be within -1 .. 2^31 - 1, got ", key_event);
+  check_arg(n_valid, "n_valid", torch::kInt32, 1);
+  check_numel(n_valid, "n_valid", 1, "one count");
+  TORCH_CHECK(n_templates >= 0 && n_templates <= SEQ_MAX_EVENTS,
+              "n_templates must be within 0 .. SEQ_MAX_EVENTS = ",
+              SEQ_MAX_EVENTS, " (a symbol is 16 bits), got ", n_templates);
+  check_arg(seq_key, "seq_key", torch::kInt64, 1);
+  const auto K = seq_key.size(0);
+  TORCH_CHECK(K >= 1 && K <= SEQ_MAX_KEYS && (K & (K - 1)) == 0,
+              "seq_key: K = max_keys must be a power of two within 1 .. ",
+              "SEQ_MAX_KEYS = ", SEQ_MAX_KEYS, ", got ", K);
+  check_arg(seq_hist, "seq_hist", torch::kInt64, 1);
+  check_numel(seq_hist, "seq_hist", K, "K");
+  TORCH_CHECK(length >= 2 && length <= SEQ_MAX_LEN,
+              "length must be within 2 .. SEQ_MAX_LEN = ", SEQ_MAX_LEN,
+              ", got ", length);
+  TORCH_CHECK(B <= INT32_MAX, "lines: B = ", B, " must be below 2^31");
+  DeviceScope dev = parsed_batch_scope(
+      lines, event_id, caps, n_caps, fmt_caps, n_fmt_caps,
+      {{"n_valid", n_valid}, {"seq_key", seq_key}, {"seq_hist", seq_hist}});
+  const auto i64 = event_id.options().dtype(torch::kInt64);
+  if (B == 0) return {torch::zeros({0}, i64), torch::zeros({0, 1}, i64)};
+  size_t temp_bytes = 0;
+  C10_HIP_CHECK(
+      dmx_seq_sort_temp_bytes((int)B, (int)K, dev.stream(), &temp_bytes));
+  // never empty: a null scratch pointer would turn the sort into a size query
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  auto sort_temp = torch::empty({(int64_t)temp_bytes},
+                                event_id.options().dtype(torch::kUInt8));
+  auto kh = torch::empty({B}, i64);
+  auto words = torch::empty({2, B}, i64);
+  // every element of both outputs is written by the grams kernel
+  auto seq_gram = torch::empty({B}, i64);
+  auto gram_hash = torch::empty({B, 1}, i64);
+  C10_HIP_CHECK(dmx_launch_event_sequence(
+      batch, (int)key_kind, (int)key_event, (int)key_pos, lower ? 1 : 0,
+      n_valid.data_ptr<int32_t>(), (int)n_templates, (int)K, (int)length,
+      seq_key.data_ptr<int64_t>(), seq_hist.data_ptr<int64_t>(),
+      kh.data_ptr<int64_t>(), words.data_ptr<int64_t>(), sort_temp.data_ptr(),
+      temp_bytes, seq_gram.data_ptr<int64_t>(), gram_hash.data_ptr<int64_t>(),
+      dev.stream()));
+  return {seq_gram, gram_hash};
+}
+
 }  // namespace
 
 void register_codec(py::module_& m);   // codec.cpp
@@ -833,6 +908,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "value ranges: fit the training rows, judge every (line, range)");
   m.def("value_range_limits", &value_range_limits,
         "limits of the value-range grammar (max_span, max_digits)");
+  m.def("event_sequence_step", &event_sequence_step,
+        "event sequences: per-key n-grams of event ids and their hashes");
+  m.def("event_sequence_limits", &event_sequence_limits,
+        "limits of event_sequence_step (max_len, max_keys, max_events)");
   m.def("edit_distance", &edit_distance,
         "batched Levenshtein distances (wavefront DP in LDS)");
 }

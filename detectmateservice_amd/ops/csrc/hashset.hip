@@ -10,32 +10,10 @@
 // Tables: [W, capacity] u64, 0 = empty (hashes are forced odd). Linear
 // probing; capacity is a power of two sized >= 4x expected cardinality.
 #include "common.h"
-#include "field_span.h"
+#include "field_hash.h"
 #include "kernels.h"
 
 #define EMPTY_KEY 0ull
-
-static __device__ __forceinline__ unsigned long long fnv1a64(
-    const unsigned char* p, int n, int lower) {
-  unsigned long long h = 1469598103934665603ull;
-  for (int i = 0; i < n; ++i) {
-    unsigned char c = p[i];
-    if (lower && c >= 'A' && c <= 'Z') c += 32;
-    h ^= (unsigned long long)c;
-    h *= 1099511628211ull;
-  }
-  return h | 1ull;  // never EMPTY_KEY
-}
-
-// Hash of the span that spec `s` watches on `line`: 0 when the spec is not
-// relevant for the line or the field is absent (field_span.h).
-static __device__ __forceinline__ unsigned long long field_hash(
-    const ParsedBatch& batch, const FieldSpec s, int line, int lower) {
-  const FieldSpan f = field_span(batch, s, line);
-  if (f.len < 0) return 0ull;
-  return fnv1a64(batch.lines + (long)line * batch.max_len + f.start, f.len,
-                 lower);
-}
 
 // For each (line, watch): the hash of the watched span.
 extern "C" __global__ __launch_bounds__(256)

@@ -32,6 +32,9 @@ constexpr int ER_MAX_EVENTS = 8192;   // event_rate: bins (32 KiB LDS histogram)
 constexpr int64_t ER_MAX_CELLS = int64_t(1) << 24;  // event_rate: NW * E
 constexpr int VR_MAX_SPAN = 17;       // value_range: bytes of a number
 constexpr int VR_MAX_DIGITS = 15;     // value_range: digits (10^15 < 2^53)
+constexpr int SEQ_MAX_LEN = 4;        // event_sequence: symbols of 16 bits
+constexpr int SEQ_MAX_KEYS = 1 << 24; // event_sequence: history buckets
+constexpr int SEQ_MAX_EVENTS = 65535; // event_sequence: a symbol is 16 bits
 
 // Dynamic LDS of dmx_template_match: the segment blob (16-B rounded) plus
 // one staged line per wave. The kernel carves its arena the same way.
@@ -220,6 +223,24 @@ void dmx_launch_value_range(ParsedBatch batch, const int32_t* specs, int R,
                             const double* slack, double* lo, double* hi,
                             int64_t* n, int train_upto, int32_t* range_code,
                             double* range_value, hipStream_t stream);
+
+// event_sequence.hip: one batch of the event-sequence stage (keys launch,
+// rocPRIM radix sort, grams launch, commit launch). The key field is a watch
+// spec by value, key_kind < 0 = no key (the stream is one sequence). n_valid:
+// device int32 [1]; T templates, K buckets (a power of two), length symbols
+// per gram. State, updated in place: seq_key, seq_hist int64 [K]. Scratch,
+// contents unspecified: kh int64 [B]; words int64 [2, B] (sort input and
+// output); sort_temp of the sort_temp_bytes that dmx_seq_sort_temp_bytes
+// reports for (B, K), never null. Outputs, fully written: seq_gram and
+// gram_hash int64 [B]. B >= 1.
+hipError_t dmx_seq_sort_temp_bytes(int B, int K, hipStream_t stream,
+                                   size_t* bytes);
+hipError_t dmx_launch_event_sequence(
+    ParsedBatch batch, int key_kind, int key_event, int key_pos, int lower,
+    const int32_t* n_valid, int T, int K, int length, int64_t* seq_key,
+    int64_t* seq_hist, int64_t* kh, int64_t* words, void* sort_temp,
+    size_t sort_temp_bytes, int64_t* seq_gram, int64_t* gram_hash,
+    hipStream_t stream);
 
 // edit_distance.hip: dist [Na, Nb] int32. A and B are [N, max_len] rows with
 // max_len <= ED_MAX_LEN; the kernel clamps every word of a_len and b_len to

@@ -11,12 +11,13 @@ TransformerDetector service uses internally per batch.
 Per batch, all on `device`: the template_match kernel (log_format header
 split + template match: event_id + capture spans), then the configured stages
 of stages.py, ``pipe.stages``, in this order: new value (watches and
-combinations), event rate, value ranges, transformer score. Launches, alert
-reasons and checkpoint keys follow that list; each stage class says what it
-computes.
+combinations), event rate, event sequence, value ranges, transformer score.
+Launches, alert reasons and checkpoint keys follow that list; each stage class
+says what it computes.
 Anomaly = NewValue unseen-value hit OR unseen combination OR transformer
-score > threshold OR, on a window's boundary line, a flagged event rate OR a
-numeric field outside its learned range.
+score > threshold OR, on a window's boundary line, a flagged event rate OR an
+n-gram of event ids never seen for the line's key OR a numeric field outside
+its learned range.
 """
 from __future__ import annotations
 
@@ -27,8 +28,8 @@ import torch
 
 from . import ops
 from .models.bert_tiny import BertTinyConfig
-from .stages import (EventRateStage, NewValueStage, TransformerStage,
-                     ValueRangeStage, marked)
+from .stages import (EventRateStage, EventSequenceStage, NewValueStage,
+                     TransformerStage, ValueRangeStage, marked)
 
 
 @dataclass
@@ -56,6 +57,12 @@ class PipelineConfig:
     #: window_lines 1000, ewma_alpha 0.3, z_threshold 4.0, min_windows 3);
     #: None = stage off, {} = on with the defaults
     event_rate: Optional[dict] = None
+    #: event sequences: {length, key, max_keys, capacity} (docs/kernels.md,
+    #: "Event sequences"): the n-gram of event ids that a line completes in
+    #: the history of its key (a field written like a `watches` entry; no
+    #: key = the whole stream) alerts when training never saw it. None =
+    #: stage off, {} = on with the defaults
+    event_sequence: Optional[dict] = None
     #: numeric value ranges: list of dicts written like `watches` entries
     #: plus the optional keys name, slack, non_numeric ("ignore" | "alert")
     #: and min / max (docs/kernels.md, "Value ranges"). The smallest and
@@ -83,16 +90,20 @@ class GpuPipeline:
         nv = NewValueStage(config, self.device)
         rate = (EventRateStage(config, self.device, len(self.matcher.templates))
                 if config.event_rate is not None else None)
+        seq = (EventSequenceStage(config, self.device, len(self.matcher.templates))
+               if config.event_sequence is not None else None)
         ranges = ValueRangeStage(config, self.device) if len(config.ranges) else None
         bert = TransformerStage(config, self.device) if config.use_transformer else None
         # the state objects under their public names (None = not configured)
         self.specs, self.members, self.combo_off, self.n_combos = (
             nv.specs, nv.members, nv.combo_off, nv.n_combos)
-        self.hashsets, self.event_rate, self.value_ranges, self.model = (
-            s.state if s else None for s in (nv, rate, ranges, bert))
+        (self.hashsets, self.event_rate, self.event_sequence,
+         self.value_ranges, self.model) = (
+            s.state if s else None for s in (nv, rate, seq, ranges, bert))
+        self.sequence_grams = seq.grams if seq else None
         self.embedding_stats = bert.stats if bert else None
         self.stages = [s for s in (nv if nv.state is not None else None,
-                                   rate, ranges, bert) if s is not None]
+                                   rate, seq, ranges, bert) if s is not None]
         self.seen_lines = 0
         # hipGraph capture state (enable_graph(); steady-state detect only)
         self._graph = self._graph_in = self._graph_out = None
@@ -108,14 +119,16 @@ class GpuPipeline:
         rate_z [NW, E] (absent otherwise: ``out.get("rate_hits")`` is None).
         With ranges configured (and only then) range_code int32 [B, R] (0 =
         nothing, 1 = below, 2 = above, 3 = not a number) and range_value f64
-        [B, R].
+        [B, R]. With event_sequence configured seq_unseen int32 [B] and
+        seq_gram int64 [B] (the line's n-gram, 16 bits per event id).
 
-        ``n_valid`` and ``rate`` concern the event-rate stage alone, the one
-        stage with stream state: only the first n_valid rows (default: all)
-        enter its windows, and ``rate=False`` skips it, so the call neither
-        moves that state nor reports rate alerts (its keys are None). The
-        first ``train_lines`` rows of the stream train; the stream position
-        ``seen_lines`` moves only here and in a graph replay."""
+        ``n_valid`` and ``rate`` concern the two stages with stream state,
+        event rate and event sequence: only the first n_valid rows (default:
+        all) enter the windows and the histories, and ``rate=False`` skips
+        both, so the call neither moves that state nor reports their alerts
+        (their keys are None). The first ``train_lines`` rows of the stream
+        train; the stream position ``seen_lines`` moves only here and in a
+        graph replay."""
         B = lines.shape[0]
         train_upto = min(B, max(0, self.config.train_lines - self.seen_lines))
         out = self._run(lines, line_len, train_upto, n_valid, rate,
@@ -127,7 +140,7 @@ class GpuPipeline:
                 threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """Judge old lines as the detect phase would, with ``threshold`` in
         place of the configured one if given: nothing trains, the event-rate
-        stage is skipped, the stream position stays."""
+        and event-sequence stages are skipped, the stream position stays."""
         return self._run(lines, lens, 0, None, False, float(
             self.config.score_threshold if threshold is None else threshold))
 
@@ -202,9 +215,9 @@ class GpuPipeline:
             (batch_size, self.config.max_len), dtype=torch.uint8, device=self.device)
         static_lens = torch.zeros((batch_size,), dtype=torch.int32, device=self.device)
         # warm up allocator/kernels on the same shapes, then capture. The
-        # event-rate stage reads its row count from a device word: 0 makes
-        # the warm-ups rewrite its state with the values it holds, and the
-        # captured launches read whatever the word holds at replay.
+        # event-rate and event-sequence stages read their row count from a
+        # device word: 0 makes the warm-ups leave their state as it is, and
+        # the captured launches read whatever the word holds at replay.
         args = (static_lines, static_lens, 0, 0, True, self.config.score_threshold)
         for _ in range(2):
             self._run(*args)

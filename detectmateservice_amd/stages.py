@@ -38,6 +38,25 @@ def straddle(B: int, train_upto: int, judge: Callable, zeros: Callable, *per_row
     return out
 
 
+def union_hashsets(hs: "ops.GpuHashSets", group) -> None:
+    """COLLECTIVE union of the data-parallel hash sets ``hs`` of every rank."""
+    import torch.distributed as tdist
+    if hasattr(hs, "tables"):  # GPU open-addressing tables
+        from .parallel.dist import all_reduce_hashsets
+        all_reduce_hashsets(hs.tables, group=group)
+    else:  # CPU fallback keeps Python sets
+        world = tdist.get_world_size(group)
+        local = [sorted(s) for s in hs.sets]
+        gathered: list = [None] * world
+        tdist.all_gather_object(gathered, local, group=group)
+        me = tdist.get_rank(group)
+        for r, other in enumerate(gathered):
+            if r == me or not other:
+                continue
+            for w, values in enumerate(other):
+                hs.sets[w].update(values)
+
+
 class Stage:
     """What the pipeline and the detector ask of a stage, next to
     ``run(lines, match, train_upto, n_valid) -> dict`` of its keys; the
@@ -124,23 +143,7 @@ class NewValueStage(Stage):
                 if host_out.get(k) is not None and int(host_out[k][i].sum()) > 0]
 
     def dist_sync(self, group):
-        """COLLECTIVE union of the data-parallel hash sets."""
-        import torch.distributed as tdist
-        hs = self.state
-        if hasattr(hs, "tables"):  # GPU open-addressing tables
-            from .parallel.dist import all_reduce_hashsets
-            all_reduce_hashsets(hs.tables, group=group)
-        else:  # CPU fallback keeps Python sets
-            world = tdist.get_world_size(group)
-            local = [sorted(s) for s in hs.sets]
-            gathered: list = [None] * world
-            tdist.all_gather_object(gathered, local, group=group)
-            me = tdist.get_rank(group)
-            for r, other in enumerate(gathered):
-                if r == me or not other:
-                    continue
-                for w, values in enumerate(other):
-                    hs.sets[w].update(values)
+        union_hashsets(self.state, group)
 
 
 class EventRateStage(Stage):
@@ -189,6 +192,67 @@ class EventRateStage(Stage):
             who = "unparsed" if e == 0 else f"event {e}"
             parts.append(f"{who}: {int(counts[e])}/window (z={float(z[e]):+.1f})")
         return ["event rate: " + "; ".join(parts)]
+
+
+class EventSequenceStage(Stage):
+    """The n-gram of event ids that each line completes within its key's
+    history (docs/kernels.md, "Event sequences") against the set of grams
+    seen in training. The per-key histories are stream state on the device
+    and move on every member row, training or not; the verdict is a probe of
+    the gram's hash, as NewValueStage probes a value's. Under data-parallel
+    ranks the gram set is united, the histories stay per rank."""
+    name = "event_sequence"
+    keys = ("seq_unseen", "seq_gram")
+    windowed = True  # a re-score of old lines must not move live histories
+
+    def __init__(self, config, device, n_templates: int) -> None:
+        unknown = set(config.event_sequence) - set(ops.EVENT_SEQUENCE_DEFAULTS)
+        if unknown:
+            raise ValueError(
+                f"unknown event_sequence key(s) {sorted(unknown)}; valid keys: "
+                f"{sorted(ops.EVENT_SEQUENCE_DEFAULTS)}")
+        p = {**ops.EVENT_SEQUENCE_DEFAULTS, **config.event_sequence}
+        self.state = ops.EventSequenceState(
+            n_templates, length=p["length"], max_keys=p["max_keys"], key=p["key"],
+            lowercase=config.lowercase, device=device)
+        capacity = int(config.hashset_capacity if p["capacity"] is None
+                       else p["capacity"])
+        if capacity < 1 or capacity & (capacity - 1):
+            raise ValueError(
+                f"event_sequence capacity must be a power of two, got {capacity}")
+        self.grams = ops.GpuHashSets(1, capacity, device=device)
+        self.parts = {"event_sequence": self.state, "sequence_grams": self.grams}
+
+    def run(self, lines, match, train_upto, n_valid):
+        gram, hashes = self.state.step(lines, match, n_valid)
+        if train_upto > 0:
+            self.grams.insert(hashes[:train_upto])
+        B = lines.shape[0]
+        unseen = straddle(
+            B, train_upto, self.grams.probe,
+            lambda: torch.zeros((B, 1), dtype=torch.int32, device=lines.device),
+            hashes)
+        return {"seq_unseen": unseen.view(B), "seq_gram": gram}
+
+    def flags(self, out):
+        unseen = out.get("seq_unseen")
+        return None if unseen is None else unseen > 0
+
+    def before_replay(self, n_rows):
+        # pad rows parse as lines of length 0; they must not enter a history
+        self.state.set_n_valid(n_rows)
+
+    def reasons(self, host_out, i):
+        """"unknown event sequence: ^ > 3 > 7 (per ses)": the gram of row i,
+        oldest event first, ^ where the key's history was still empty."""
+        unseen = host_out.get("seq_unseen")
+        if unseen is None or int(unseen[i]) <= 0:
+            return []
+        symbols = ops.decode_gram(int(host_out["seq_gram"][i]), self.state.length)
+        return [ops.sequence_text(symbols, self.state.key_name)]
+
+    def dist_sync(self, group):
+        union_hashsets(self.grams, group)
 
 
 class ValueRangeStage(Stage):

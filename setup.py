@@ -30,6 +30,7 @@ sources = [
     str(CSRC / "hashset.hip"),
     str(CSRC / "event_rate.hip"),
     str(CSRC / "value_range.hip"),
+    str(CSRC / "event_sequence.hip"),
     str(CSRC / "edit_distance.hip"),
 ]
 
