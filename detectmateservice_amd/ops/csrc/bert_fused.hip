@@ -15,14 +15,18 @@
 // domains) and one block's barrier wait overlaps the other's compute.
 //
 // Arena (the Tile aliases below): x | buf | vt, bf16, then [H] f32 for
-// pooling. `buf` has three tenants in turn: Q|K; then the per-wave P tiles
-// followed by the attention output; then one FFN half. V never enters buf:
+// pooling. vt holds V^T through attention and x + the first FFN half
+// between the two W2 GEMMs. `buf` has three tenants in turn: Q|K; then the
+// per-wave P tiles followed by the attention output; then one FFN half. V
+// never enters buf:
 // the qkv GEMM writes it transposed into vt, k-contiguous for the P.V MFMA.
 //
 // Schedule (bert_fused_body; every `|` is a block barrier):
 //   embed | per layer: qkv | attention (one barrier inside, before the P
 //   tiles overwrite Q|K) | x += Wo | LN1 | 2 x (W1 half + GELU | x += W2
-//   half |) LN2 | pool | score. dmx_bert_fused_embed_bf16 runs the same
+//   half |) LN2 | pool | score. Both W1 halves read the LN1 output: the first
+//   W2 half writes x + its update to XMid, not over x, and the second adds
+//   its update to XMid and writes x. dmx_bert_fused_embed_bf16 runs the same
 //   schedule and ends in pool_embed instead: the pooled vector and / or its
 //   distance from a fitted diagonal Gaussian.
 //
@@ -90,6 +94,9 @@ using AttnOut = Tile<PTiles::END, BF_S, BF_H, XS>;
 // buf, third tenant
 using FfnHalf = Tile<XTile::END, BF_S, BF_FFN / 2, QKS>;
 using VtTile = Tile<AttnOut::END, 2 * BF_DH, BF_S, VTS>;  // after buf
+// vt, second tenant (V^T is dead once attention is done): x + W2 half 0,
+// while x itself still feeds the W1 GEMM of half 1
+using XMid = Tile<VtTile::OFF, BF_S, BF_H, XS>;
 constexpr int RED_OFF = VtTile::END;                      // [H] f32 pooling
 
 static_assert(QkTile::END <= VtTile::OFF, "Q|K runs past buf");
@@ -98,6 +105,7 @@ static_assert(PTiles::END <= AttnOut::OFF,
               "the P tiles reach into the attention output");
 static_assert(AttnOut::END <= VtTile::OFF,
               "the attention output runs past buf");
+static_assert(XMid::END <= VtTile::END, "XMid runs past vt");
 static_assert(BF_LDS_BYTES == RED_OFF * sizeof(short) + BF_H * sizeof(float),
               "kernels.h BF_LDS_BYTES out of step with the LDS strides");
 // The weight-first GEMMs fetch four biases with one 16-byte load: every
@@ -146,7 +154,9 @@ static __device__ __forceinline__ short4v pack_bf16x4(f32x4 v) {
 
 // ---- in-block GEMM: out = act(in_lds[64][K] @ Wt[N][WTS] + bias) ---------
 // MODE 0: write out_lds[m][n]; MODE 1 (qkv): n<2H -> out (Q|K), else vt
-// transposed; MODE 2: x[m][n] += v (residual-accumulate). ACT 1 = GELU.
+// transposed; MODE 2: x[m][n] += v (residual-accumulate); MODE 3:
+// out[m][n] = x[m][n] + v, rows XS apart (residual-accumulate into another
+// tile, x left as it is). ACT 1 = GELU.
 // ABL (perf-ablation diagnostics, numerically wrong on purpose):
 // bit 1 = B operand from an opaque register instead of the L2 weight
 // load (removes vmcnt parks); bit 2 = A operand from a register instead
@@ -158,8 +168,9 @@ static __device__ __forceinline__ short4v pack_bf16x4(f32x4 v) {
 // fragment per quad and cannot hoist reads across the quad boundary. The
 // caller guarantees in_lds never overlaps this GEMM's outputs.
 //
-// SWAP is the weight-first operand order of the file header: MODE 0, MODE 2
-// and the Q|K columns of MODE 1 run swapped, the V columns of MODE 1 do not.
+// SWAP is the weight-first operand order of the file header: MODE 0, MODE 2,
+// MODE 3 and the Q|K columns of MODE 1 run swapped, the V columns of MODE 1
+// do not.
 //
 // The three functions below keep one scalar argument list and spell their
 // fragment addresses out instead of using lds_frag / lds_quad. Every call
@@ -233,6 +244,12 @@ static __device__ __forceinline__ void gemm_quad(
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] += bf16_to_f32(xv[r]);
       *px = pack_bf16x4(v);
+    } else if constexpr (MODE == 3) {
+      const int off = (fm * 16 + l15) * XS + fn * 16 + l4 * 4;
+      const short4v xv = *(const lds_short4*)(x_lds + off);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] += bf16_to_f32(xv[r]);
+      *(lds_short4*)(out_lds + off) = pack_bf16x4(v);
     } else {
       if constexpr (ACT == 1) {
 #pragma unroll
@@ -623,7 +640,9 @@ static __device__ __forceinline__ void bert_fused_body(
     __syncthreads();
     stamp.mark();
 
-    // FFN in two K=256 halves: buf = gelu(x @ W1_h); x += buf @ W2_h; LN2
+    // FFN in two K=256 halves, both reading the LN1 output in x:
+    // buf = gelu(x @ W1_0); XMid = x + buf @ W2_0 + b2;
+    // buf = gelu(x @ W1_1); x = XMid + buf @ W2_1; LN2
     if (PHASES & PH_FFN)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -636,13 +655,13 @@ static __device__ __forceinline__ void bert_fused_body(
       // (compile-time: a runtime null test on the pointer, a VGPR in the
       // noinline callee, put an exec-mask branch in front of every quad)
       if (h == 0)
-        block_gemm<BF_FFN / 2, BF_H, 2, 0, BF_FFN, ABL, true>(
+        block_gemm<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, true>(
             FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2), (glob_cfloat*)(lf + FB_B2),
-            nullptr, 0, x, nullptr, wid, lane);
+            XMid::ptr(), XS, x, nullptr, wid, lane);
       else
-        block_gemm<BF_FFN / 2, BF_H, 2, 0, BF_FFN, ABL, false>(
+        block_gemm<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, false>(
             FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2 + (long)h * (BF_FFN / 2)),
-            nullptr, nullptr, 0, x, nullptr, wid, lane);
+            nullptr, x, XS, XMid::ptr(), nullptr, wid, lane);
       __syncthreads();
     }
     if (PHASES & PH_LN)
