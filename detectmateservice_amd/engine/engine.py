@@ -27,11 +27,11 @@ import logging
 import os
 import threading
 import time
-from typing import List, Optional, Protocol, runtime_checkable
+from typing import Any, Callable, List, NamedTuple, Optional, Protocol, runtime_checkable
 
 from ..settings import ServiceSettings
 from ..utils.metrics import ServiceMetrics
-from .sockets import PairSocketFactory, RecvTimeout, SocketClosed
+from .sockets import PackedBatch, PairSocketFactory, RecvTimeout, SocketClosed
 
 
 class EngineException(Exception):
@@ -53,6 +53,56 @@ def _count_lines(data: bytes) -> int:
     frames; we floor at 1 so lines/sec matches frames of protobuf traffic)."""
     n = data.count(b"\n")
     return n if n > 0 else 1
+
+
+class _LoopStats:
+    """DMX_ENGINE_STATS=1 window (perf triage): named timers summed over ~2 s
+    of batches; a loop logs its own line when ``due``, then calls ``reset``."""
+
+    def __init__(self, *timers: str) -> None:
+        self.on = os.environ.get("DMX_ENGINE_STATS") == "1"
+        self._names = timers
+        self.reset(time.perf_counter())
+
+    def reset(self, now: float) -> None:
+        self.n = self.frames = 0  # batches, their frames
+        self.t = dict.fromkeys(self._names, 0.0)
+        self._last = now
+
+    def add(self, timer: str, seconds: float) -> None:
+        if self.on:
+            self.t[timer] += seconds
+
+    def batch(self, frames: int, proc_seconds: float) -> None:
+        if self.on:
+            self.n += 1
+            self.frames += frames
+            self.t["proc"] += proc_seconds
+
+    def due(self, now: float) -> bool:
+        return self.on and self.n > 0 and now - self._last > 2.0
+
+    def ms(self, timer: str) -> float:
+        return self.t[timer] * 1e3 / self.n  # mean per batch
+
+
+class _PackedPlane(NamedTuple):
+    """What ``Engine._probe_packed`` resolved for the packed loop."""
+
+    process: Callable                # process_packed_frames
+    submit: Optional[Callable]       # submit_/collect_packed_frames: both
+    collect: Optional[Callable]      # or neither (then not pipelined)
+    reply_conn: Callable             # socket.reply_conn, else its send
+    has_pending: Callable            # socket.has_pending, else "no"
+
+
+class _InFlight(NamedTuple):
+    """A submitted, not yet collected batch. It holds the batch itself, so
+    its replies use ITS routes whatever the listener received since."""
+
+    token: Any
+    batch: PackedBatch
+    t_submit: float
 
 
 class Engine:
@@ -80,6 +130,9 @@ class Engine:
         self._stop_event = threading.Event()
         self._thread: Optional[threading.Thread] = None
         self._running = False
+        #: set by the packed loop for its _emit/_drain/_submit methods
+        self._plane: Optional[_PackedPlane] = None
+        self._stats: Optional[_LoopStats] = None
 
         # Bind the input socket now (reference engine.py:111-117); on any
         # failure during output setup, close the input to avoid leaks
@@ -162,9 +215,41 @@ class Engine:
             return self._run_dist_loop()
         if self.settings.engine_source_mode:
             return self._run_source_loop()
-        if self.settings.engine_packed_mode and self._try_packed_loop():
-            return
+        if self.settings.engine_packed_mode:
+            plane = self._probe_packed()
+            if plane is not None:
+                return self._run_packed_loop(plane)
         return self._run_socket_loop()
+
+    # -- accounting every loop shares -----------------------------------
+    def _count_read(self, n_bytes: int, n_lines: int,
+                    batch_size: Optional[int] = None) -> None:
+        """``batch_size`` feeds the batch-size histogram; the dist loops,
+        which never observed it, pass none."""
+        m = self.metrics
+        m.data_read_bytes_total.inc(n_bytes)
+        m.data_read_lines_total.inc(n_lines)
+        if batch_size is not None:
+            m.engine_batch_size.observe(batch_size)
+
+    def _count_processed(self, n_bytes: int, n_lines: int, elapsed: float) -> None:
+        m = self.metrics
+        m.data_processed_bytes_total.inc(n_bytes)
+        m.data_processed_lines_total.inc(n_lines)
+        m.observe_batch(elapsed, n_lines)
+
+    def _count_written(self, out: bytes, ok: bool, n_lines: int = 0) -> None:
+        """One output written (``ok``) or dropped. It counts as
+        ``_count_lines(out)`` lines unless the caller says how many:
+        packed alerts and dist hops count 1 per output."""
+        m = self.metrics
+        n_lines = n_lines or _count_lines(out)
+        if ok:
+            m.data_written_bytes_total.inc(len(out))
+            m.data_written_lines_total.inc(n_lines)
+        else:
+            m.data_dropped_bytes_total.inc(len(out))
+            m.data_dropped_lines_total.inc(n_lines)
 
     def _run_socket_loop(self) -> None:
         """The plain batched frame loop (also the elastic-degradation
@@ -176,10 +261,10 @@ class Engine:
             s.engine_addr, s.engine_batch_size, s.engine_batch_linger_ms,
             len(self._out_socks),
         )
-        # DMX_ENGINE_STATS=1: per-batch stage timing every ~2 s (perf triage)
-        stats_on = os.environ.get("DMX_ENGINE_STATS") == "1"
-        st = {"n": 0, "frames": 0, "recv": 0.0, "proc": 0.0, "other": 0.0,
-              "last": time.perf_counter()}
+        sock = self._pair_sock
+        # a socket without per-frame reply(idx) answers its last sender
+        reply = getattr(sock, "reply", lambda idx, out: sock.send(out, block=False))
+        stats = _LoopStats("recv", "proc", "total")
         t_end = time.perf_counter()
         while not self._stop_event.is_set():
             try:
@@ -187,8 +272,7 @@ class Engine:
                 frames = self._pair_sock.recv_many(
                     s.engine_batch_size, s.engine_recv_timeout, s.engine_batch_linger_ms
                 )
-                if stats_on:
-                    st["recv"] += time.perf_counter() - t_r0
+                stats.add("recv", time.perf_counter() - t_r0)
             except RecvTimeout:
                 continue
             except SocketClosed:
@@ -198,13 +282,11 @@ class Engine:
                     break
                 self._log.error("recv error: %s", exc)
                 continue
-            if not frames:
-                continue
             # Skip empty frames (reference engine.py:207-209) — but keep
-            # each surviving frame's ORIGINAL batch index: the listener's
-            # _batch_conns was recorded for the unfiltered recv_many batch,
-            # so reply(i) must be given pre-filter indices or multi-peer
-            # replies route to the wrong sender.
+            # each surviving frame's ORIGINAL batch index: the listener
+            # recorded its per-frame conns for the unfiltered recv_many
+            # batch, so reply(i) must be given pre-filter indices or
+            # multi-peer replies route to the wrong sender.
             orig_idx = [i for i, f in enumerate(frames) if f]
             if len(orig_idx) != len(frames):
                 frames = [frames[i] for i in orig_idx]
@@ -213,9 +295,7 @@ class Engine:
 
             read_bytes = sum(len(f) for f in frames)
             read_lines = sum(_count_lines(f) for f in frames)
-            m.data_read_bytes_total.inc(read_bytes)
-            m.data_read_lines_total.inc(read_lines)
-            m.engine_batch_size.observe(len(frames))
+            self._count_read(read_bytes, read_lines, len(frames))
 
             t0 = time.perf_counter()
             try:
@@ -225,9 +305,7 @@ class Engine:
                 self._log.error("processing error on batch of %d: %s", len(frames), exc)
                 continue
             elapsed = time.perf_counter() - t0
-            m.data_processed_bytes_total.inc(read_bytes)
-            m.data_processed_lines_total.inc(read_lines)
-            m.observe_batch(elapsed, read_lines)
+            self._count_processed(read_bytes, read_lines, elapsed)
 
             for i, out in enumerate(outs):
                 if out is None:
@@ -237,143 +315,83 @@ class Engine:
                 else:
                     # request/reply fallback mode (engine.py:248-264);
                     # replies route to EACH frame's sender (multi-peer)
-                    reply = getattr(self._pair_sock, "reply", None)
-                    ok = (reply(orig_idx[i], out) if reply is not None
-                          else self._pair_sock.send(out, block=False))
-                    if ok:
-                        m.data_written_bytes_total.inc(len(out))
-                        m.data_written_lines_total.inc(_count_lines(out))
-                    else:
-                        m.data_dropped_bytes_total.inc(len(out))
-                        m.data_dropped_lines_total.inc(_count_lines(out))
-            if stats_on:
+                    self._count_written(out, reply(orig_idx[i], out))
+            if stats.on:
                 now = time.perf_counter()
-                st["n"] += 1
-                st["frames"] += len(frames)
-                st["proc"] += elapsed
-                st["other"] += (now - t_end) if t_end else 0.0
+                stats.batch(len(frames), elapsed)
+                stats.add("total", now - t_end)
                 t_end = now
-                if now - st["last"] > 2.0 and st["n"]:
-                    tot = st["other"]
+                if stats.due(now):
+                    tot = stats.t["total"]
                     self._log.info(
                         "[stats] %d batches (%.0f fr/batch): recv-wait %.1fms/b, "
                         "process %.1fms/b, other %.1fms/b, %.0f lines/s",
-                        st["n"], st["frames"] / st["n"],
-                        st["recv"] * 1e3 / st["n"], st["proc"] * 1e3 / st["n"],
-                        (tot - st["recv"] - st["proc"]) * 1e3 / st["n"],
-                        st["frames"] / tot if tot > 0 else 0.0,
+                        stats.n, stats.frames / stats.n,
+                        stats.ms("recv"), stats.ms("proc"),
+                        stats.ms("total") - stats.ms("recv") - stats.ms("proc"),
+                        stats.frames / tot if tot > 0 else 0.0,
                     )
-                    st.update(n=0, frames=0, recv=0.0, proc=0.0, other=0.0,
-                              last=now)
+                    stats.reset(now)
         self._log.info("engine loop exited")
 
-    def _try_packed_loop(self) -> bool:
-        """Native packed data plane: reader threads decode LogSchema frames
-        straight into tensors (frame_reader.cpp read_batch_packed); the
-        loop hands (lines, lens, ids) to the component with ZERO per-frame
-        Python objects. Requires a plain fd listener, the C++ extension
-        and a component exposing ``process_packed_frames``. Returns False
-        (caller falls back to the frame loop) when unavailable."""
-        s = self.settings
-        m = self.metrics
-        proc = getattr(self.processor, "process_packed_frames", None)
-        supports = getattr(self.processor, "supports_packed_frames", None)
-        if proc is None or (supports is not None and not supports()):
+    # -- native packed data plane ----------------------------------------
+    def _probe_packed(self) -> Optional[_PackedPlane]:
+        """The packed plane needs a component with ``process_packed_frames``
+        and a listener that can decode socket→tensor (plain fd or shm, with
+        the C++ extension); else warn, and None selects the frame loop."""
+        s, p, sock = self.settings, self.processor, self._pair_sock
+        process = getattr(p, "process_packed_frames", None)
+        supports = getattr(p, "supports_packed_frames", None)
+        if process is None or (supports is not None and not supports()):
             self._log.warning(
                 "engine_packed_mode: component has no process_packed_frames; "
                 "using the frame loop"
             )
-            return False
-        enable = getattr(self._pair_sock, "enable_packed", None)
-        max_len = getattr(self.processor, "packed_max_len", lambda: 256)()
-        pin = getattr(self.processor, "packed_pin_memory", lambda: False)()
+            return None
+        enable = getattr(sock, "enable_packed", None)
+        max_len = getattr(p, "packed_max_len", lambda: 256)()
+        pin = getattr(p, "packed_pin_memory", lambda: False)()
         if enable is None or not enable(max_len, pin, s.engine_batch_size):
             self._log.warning(
                 "engine_packed_mode: listener cannot enable the packed path "
                 "(TLS/ws/inproc or extension missing); using the frame loop"
             )
-            return False
+            return None
         # pipelined mode: overlap batch N's async GPU work with batch
         # N+1's recv+decode (submit launches without syncing; collect
         # does the one readback). Falls back to the synchronous call
         # when the component lacks the split API.
-        submit = getattr(self.processor, "submit_packed_frames", None)
-        collect = getattr(self.processor, "collect_packed_frames", None)
-        pipelined = submit is not None and collect is not None
+        submit = getattr(p, "submit_packed_frames", None)
+        collect = getattr(p, "collect_packed_frames", None)
+        if submit is None or collect is None:
+            submit = collect = None
         self._log.info(
             "engine PACKED loop started on %s (max_len=%d pin=%s pipelined=%s)",
-            s.engine_addr, max_len, pin, pipelined)
-        stats_on = os.environ.get("DMX_ENGINE_STATS") == "1"
-        st = {"n": 0, "frames": 0, "recv": 0.0, "proc": 0.0,
-              "submit": 0.0, "drain": 0.0, "last": time.perf_counter()}
-        prev = None          # in-flight token
-        prev_meta = None     # (B, nbytes, t_submit, conn, conn_segs)
-        reply_conn = getattr(self._pair_sock, "reply_conn", None)
+            s.engine_addr, max_len, pin, submit is not None)
+        return _PackedPlane(
+            process, submit, collect,
+            getattr(sock, "reply_conn", lambda conn, out: sock.send(out, block=False)),
+            # a socket that cannot tell counts as idle: drain at once
+            getattr(sock, "has_pending", lambda: False))
 
-        def emit(alerts, conn=None, segs=None):
-            # segs = [(conn, row_count)] captured AT RECV TIME for this
-            # batch (the listener's own state may already describe the
-            # NEXT batch when pipelining): merged multi-peer chunks route
-            # each alert row to ITS sender.
-            for idx, out in alerts:
-                if self._out_socks:
-                    self._send_to_outputs(out)
-                else:
-                    target = conn
-                    if segs is not None and len(segs) > 1:
-                        base = 0
-                        for c, rows in segs:
-                            if idx < base + rows:
-                                target = c
-                                break
-                            base += rows
-                    ok = (reply_conn(target, out) if reply_conn is not None
-                          else self._pair_sock.send(out, block=False))
-                    if ok:
-                        m.data_written_bytes_total.inc(len(out))
-                        m.data_written_lines_total.inc(1)
-                    else:
-                        m.data_dropped_bytes_total.inc(len(out))
-                        m.data_dropped_lines_total.inc(1)
-
-        def drain_prev():
-            nonlocal prev, prev_meta
-            if prev is None:
-                return
-            pB, pbytes, t_sub, pconn, psegs = prev_meta
-            t_d0 = time.perf_counter() if stats_on else 0.0
-            try:
-                emit(collect(prev), pconn, psegs)
-            except Exception as exc:  # noqa: BLE001
-                m.processing_errors_total.inc(pB)
-                self._log.error("processing error on packed batch of %d: %s",
-                                pB, exc)
-                prev, prev_meta = None, None
-                return
-            m.data_processed_bytes_total.inc(pbytes)
-            m.data_processed_lines_total.inc(pB)
-            m.observe_batch(time.perf_counter() - t_sub, pB)
-            if stats_on:
-                st["n"] += 1
-                st["frames"] += pB
-                st["proc"] += time.perf_counter() - t_sub
-                st["drain"] += time.perf_counter() - t_d0
-            prev, prev_meta = None, None
-
+    def _run_packed_loop(self, plane: _PackedPlane) -> None:
+        """Reader threads decode LogSchema frames straight into tensors
+        (frame_reader.cpp read_batch_packed); the loop hands (lines, lens,
+        ids) to the component with ZERO per-frame Python objects. At most
+        one batch is in flight: it is drained before the next submit, on
+        an idle or empty receive, and on exit."""
+        s = self.settings
+        self._plane = plane
+        stats = self._stats = _LoopStats("recv", "proc", "submit", "drain")
+        inflight: Optional[_InFlight] = None
         while not self._stop_event.is_set():
             try:
                 t_r0 = time.perf_counter()
-                conn, lines, lens, blob, off, nbytes = (
-                    self._pair_sock.recv_packed(
-                        s.engine_recv_timeout, s.engine_batch_size,
-                        s.engine_batch_linger_ms,
-                    )
-                )
-                if stats_on:
-                    st["recv"] += time.perf_counter() - t_r0
+                batch = self._pair_sock.recv_packed(
+                    s.engine_recv_timeout, s.engine_batch_size, s.engine_batch_linger_ms)
+                stats.add("recv", time.perf_counter() - t_r0)
             except RecvTimeout:
-                drain_prev()  # idle: finish the in-flight batch
-                continue
+                batch = None
             except SocketClosed:
                 break
             except OSError as exc:
@@ -381,68 +399,92 @@ class Engine:
                     break
                 self._log.error("recv error: %s", exc)
                 continue
-            B = int(lines.shape[0])
-            if B == 0:
-                drain_prev()
+            B = int(batch.lines.shape[0]) if batch is not None else 0
+            if B == 0:  # idle, or an empty batch: finish the in-flight one
+                self._drain(inflight)
+                inflight = None
                 continue
-            m.data_read_bytes_total.inc(nbytes)
-            m.data_read_lines_total.inc(B)
-            m.engine_batch_size.observe(B)
-            segs = getattr(self._pair_sock, "_batch_conn_segs", None)
+            self._count_read(batch.nbytes, B, B)
             t0 = time.perf_counter()
-            if pipelined:
-                drain_prev()  # collect batch N (GPU overlapped our recv)
-                try:
-                    prev = submit(lines, lens, blob, off)
-                    prev_meta = (B, nbytes, t0, conn, segs)
-                    if stats_on:
-                        st["submit"] += time.perf_counter() - t0
-                except Exception as exc:  # noqa: BLE001
-                    m.processing_errors_total.inc(B)
-                    self._log.error(
-                        "processing error on packed batch of %d: %s", B, exc)
-                    prev, prev_meta = None, None
+            if plane.submit is None:
+                self._process_packed(batch, t0)
+            else:
+                # collect batch N (the GPU overlapped our recv), launch N+1
+                self._drain(inflight)
+                inflight = self._submit(batch, t0)
                 # sparse traffic: if nothing else is already queued,
                 # finish this batch NOW instead of waiting out the recv
                 # timeout (keeps single-frame round-trip latency low;
                 # under load the queue is non-empty and pipelining holds)
-                has_pending = getattr(self._pair_sock, "has_pending", None)
-                if has_pending is None or not has_pending():
-                    drain_prev()
-            else:
-                try:
-                    alerts = proc(lines, lens, blob, off)
-                except Exception as exc:  # noqa: BLE001 - loop must survive
-                    m.processing_errors_total.inc(B)
-                    self._log.error(
-                        "processing error on packed batch of %d: %s", B, exc)
-                    continue
-                elapsed = time.perf_counter() - t0
-                m.data_processed_bytes_total.inc(nbytes)
-                m.data_processed_lines_total.inc(B)
-                m.observe_batch(elapsed, B)
-                emit(alerts, conn, segs)
-                if stats_on:
-                    st["n"] += 1
-                    st["frames"] += B
-                    st["proc"] += elapsed
-            if stats_on:
-                now = time.perf_counter()
-                if now - st["last"] > 2.0 and st["n"]:
-                    self._log.info(
-                        "[packed-stats] %d batches (%.0f fr/b): recv-wait "
-                        "%.1fms/b process %.1fms/b "
-                        "(submit %.1f drain %.1f)",
-                        st["n"], st["frames"] / st["n"],
-                        st["recv"] * 1e3 / st["n"], st["proc"] * 1e3 / st["n"],
-                        st["submit"] * 1e3 / st["n"], st["drain"] * 1e3 / st["n"],
-                    )
-                    st.update(n=0, frames=0, recv=0.0, proc=0.0,
-                              submit=0.0, drain=0.0, last=now)
-        drain_prev()
+                if not plane.has_pending():
+                    self._drain(inflight)
+                    inflight = None
+            now = time.perf_counter() if stats.on else 0.0
+            if stats.due(now):
+                self._log.info(
+                    "[packed-stats] %d batches (%.0f fr/b): recv-wait %.1fms/b "
+                    "process %.1fms/b (submit %.1f drain %.1f)",
+                    stats.n, stats.frames / stats.n, stats.ms("recv"),
+                    stats.ms("proc"), stats.ms("submit"), stats.ms("drain"))
+                stats.reset(now)
+        self._drain(inflight)
         self._log.info("engine packed loop exited")
-        return True
 
+    def _packed_error(self, batch: PackedBatch, exc: Exception) -> None:
+        """A component error costs its batch; the loop must survive."""
+        B = int(batch.lines.shape[0])
+        self.metrics.processing_errors_total.inc(B)
+        self._log.error("processing error on packed batch of %d: %s", B, exc)
+
+    def _process_packed(self, batch: PackedBatch, t0: float) -> None:
+        """Synchronous branch: the component lacks submit/collect."""
+        try:
+            alerts = self._plane.process(batch.lines, batch.lens,
+                                         batch.ids_blob, batch.ids_off)
+        except Exception as exc:  # noqa: BLE001
+            return self._packed_error(batch, exc)
+        elapsed = time.perf_counter() - t0
+        B = int(batch.lines.shape[0])
+        self._count_processed(batch.nbytes, B, elapsed)
+        self._emit(alerts, batch)
+        self._stats.batch(B, elapsed)
+
+    def _submit(self, batch: PackedBatch, t0: float) -> Optional[_InFlight]:
+        """Launch ``batch`` without syncing; None when the component raised."""
+        try:
+            token = self._plane.submit(batch.lines, batch.lens,
+                                       batch.ids_blob, batch.ids_off)
+        except Exception as exc:  # noqa: BLE001
+            return self._packed_error(batch, exc)
+        self._stats.add("submit", time.perf_counter() - t0)
+        return _InFlight(token, batch, t0)
+
+    def _emit(self, alerts, batch: PackedBatch) -> None:
+        """Send each (row, alert): to the outputs, or back to the row's
+        sender as ``batch`` recorded it."""
+        for idx, out in alerts:
+            if self._out_socks:
+                self._send_to_outputs(out)
+            else:
+                ok = self._plane.reply_conn(batch.conn_of(idx), out)
+                self._count_written(out, ok, 1)
+
+    def _drain(self, inflight: Optional[_InFlight]) -> None:
+        """Collect a submitted batch and emit its alerts (no-op for None).
+        The caller forgets ``inflight`` afterwards, also after an error."""
+        if inflight is None:
+            return
+        batch = inflight.batch
+        t_d0 = time.perf_counter()
+        try:
+            self._emit(self._plane.collect(inflight.token), batch)
+        except Exception as exc:  # noqa: BLE001
+            return self._packed_error(batch, exc)
+        now = time.perf_counter()
+        B = int(batch.lines.shape[0])
+        self._count_processed(batch.nbytes, B, now - inflight.t_submit)
+        self._stats.batch(B, now - inflight.t_submit)
+        self._stats.add("drain", now - t_d0)
 
     # ------------------------------------------------------------------
     # settings-driven distributed placement (dist_mode fanout/stage):
@@ -458,8 +500,6 @@ class Engine:
         from ..parallel import dist as dmx_dist
 
         ctx = self._dist_ctx
-        s = self.settings
-        m = self.metrics
         device = torch.device("cpu")
         if tdist.get_backend() == "nccl":
             device = torch.device("cuda", torch.cuda.current_device())
@@ -487,9 +527,26 @@ class Engine:
             return self._run_socket_loop()
         self._log.info("engine dist loop exited")
 
+    def _dist_process(self, frames: List[bytes]) -> List[bytes]:
+        """What the head and the sink do with a non-empty batch: count it
+        read, process under the error guard, count it processed (also
+        after an error, which yields no outputs). None results drop."""
+        n_bytes = sum(len(f) for f in frames)
+        self._count_read(n_bytes, len(frames))
+        t0 = time.perf_counter()
+        try:
+            outs = [o for o in self.processor.process_batch(frames)
+                    if o is not None]
+        except Exception as exc:  # noqa: BLE001
+            self.metrics.processing_errors_total.inc(len(frames))
+            self._log.error("dist processing error: %s", exc)
+            outs = []
+        self._count_processed(n_bytes, len(frames), time.perf_counter() - t0)
+        return outs
+
     def _dist_head_loop(self, dmx_dist, mode, rank, world, device) -> bool:
         """Returns True when the collective path failed (degrade)."""
-        s, m = self.settings, self.metrics
+        s = self.settings
         degraded = False
         while not self._stop_event.is_set():
             try:
@@ -501,22 +558,7 @@ class Engine:
             except SocketClosed:
                 break
             frames = [f for f in frames if f]
-            outs: List[bytes] = []
-            if frames:
-                n_bytes = sum(len(f) for f in frames)
-                m.data_read_bytes_total.inc(n_bytes)
-                m.data_read_lines_total.inc(len(frames))
-                t0 = time.perf_counter()
-                try:
-                    outs = [o for o in self.processor.process_batch(frames)
-                            if o is not None]
-                except Exception as exc:  # noqa: BLE001
-                    m.processing_errors_total.inc(len(frames))
-                    self._log.error("dist processing error: %s", exc)
-                    outs = []
-                m.data_processed_bytes_total.inc(n_bytes)
-                m.data_processed_lines_total.inc(len(frames))
-                m.observe_batch(time.perf_counter() - t0, max(len(frames), 1))
+            outs = self._dist_process(frames) if frames else []
             flag = dmx_dist.FRAME_DATA if outs else dmx_dist.FRAME_HEARTBEAT
             try:
                 if mode == "fanout":
@@ -527,10 +569,8 @@ class Engine:
                 self._log.error("dist send failed (peer lost?): %s", exc)
                 degraded = True
                 break
-            if outs:
-                nb = sum(len(o) for o in outs)
-                m.data_written_bytes_total.inc(nb)
-                m.data_written_lines_total.inc(len(outs))
+            for out in outs:
+                self._count_written(out, True, 1)
         # wake every peer out of its collective before exiting
         try:
             if mode == "fanout":
@@ -546,7 +586,6 @@ class Engine:
     def _dist_sink_loop(self, dmx_dist, mode, rank, world, src,
                         device) -> bool:
         """Returns True when the collective path failed (degrade)."""
-        m = self.metrics
         last = mode == "fanout" or rank == world - 1
         degraded = False
         while not self._stop_event.is_set():
@@ -567,22 +606,7 @@ class Engine:
                     except RuntimeError:
                         pass
                 break
-            outs: List[bytes] = []
-            if frames:
-                n_bytes = sum(len(f) for f in frames)
-                m.data_read_bytes_total.inc(n_bytes)
-                m.data_read_lines_total.inc(len(frames))
-                t0 = time.perf_counter()
-                try:
-                    outs = [o for o in self.processor.process_batch(frames)
-                            if o is not None]
-                except Exception as exc:  # noqa: BLE001
-                    m.processing_errors_total.inc(len(frames))
-                    self._log.error("dist processing error: %s", exc)
-                    outs = []
-                m.data_processed_bytes_total.inc(n_bytes)
-                m.data_processed_lines_total.inc(len(frames))
-                m.observe_batch(time.perf_counter() - t0, max(len(frames), 1))
+            outs = self._dist_process(frames) if frames else []
             if mode == "stage" and not last:
                 flag = (dmx_dist.FRAME_DATA if outs
                         else dmx_dist.FRAME_HEARTBEAT)
@@ -592,9 +616,8 @@ class Engine:
                     self._log.error("dist forward failed: %s", exc)
                     degraded = True
                     break
-                if outs:
-                    m.data_written_bytes_total.inc(sum(len(o) for o in outs))
-                    m.data_written_lines_total.inc(len(outs))
+                for out in outs:
+                    self._count_written(out, True, 1)
             else:
                 for out in outs:
                     self._send_to_outputs(out)
@@ -606,7 +629,6 @@ class Engine:
         The input socket stays bound (admin/back-channel parity) but the
         data flows component → outputs."""
         s = self.settings
-        m = self.metrics
         gen = self.processor.source_batches(s.engine_batch_size, self._stop_event)
         self._log.info("engine source loop started (outputs=%d)", len(self._out_socks))
         for batch in gen:
@@ -615,20 +637,16 @@ class Engine:
             t0 = time.perf_counter()
             n_bytes = sum(len(f) for f in batch)
             n_lines = sum(_count_lines(f) for f in batch)
-            m.data_read_bytes_total.inc(n_bytes)
-            m.data_read_lines_total.inc(n_lines)
-            m.data_processed_bytes_total.inc(n_bytes)
-            m.data_processed_lines_total.inc(n_lines)
-            m.engine_batch_size.observe(len(batch))
+            self._count_read(n_bytes, n_lines, len(batch))
             for out in batch:
                 self._send_to_outputs(out)
-            m.observe_batch(time.perf_counter() - t0, n_lines)
+            # "processing" a generated batch is sending it on
+            self._count_processed(n_bytes, n_lines, time.perf_counter() - t0)
         self._log.info("engine source loop exited")
 
     def _send_to_outputs(self, data: bytes) -> None:
         """Broadcast to all outputs with retry-then-drop per socket
         (reference engine.py:266-302)."""
-        m = self.metrics
         for sock in self._out_socks:
             sent = False
             for _attempt in range(self.settings.engine_retry_count):
@@ -639,10 +657,6 @@ class Engine:
                 except SocketClosed:
                     break
                 time.sleep(0.01)
-            if sent:
-                m.data_written_bytes_total.inc(len(data))
-                m.data_written_lines_total.inc(_count_lines(data))
-            else:
-                m.data_dropped_bytes_total.inc(len(data))
-                m.data_dropped_lines_total.inc(_count_lines(data))
+            self._count_written(data, sent)
+            if not sent:
                 self._log.debug("dropped frame for %s", sock.addr)

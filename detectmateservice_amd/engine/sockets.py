@@ -43,7 +43,7 @@ import struct
 import threading
 import time
 from pathlib import Path
-from typing import Dict, List, Optional, Protocol, Tuple, runtime_checkable
+from typing import Any, Dict, List, NamedTuple, Optional, Protocol, Tuple, runtime_checkable
 
 from ..settings import EngineAddr, TlsInputConfig, TlsOutputConfig
 
@@ -89,6 +89,35 @@ class EngineSocket(Protocol):
     def recv(self, timeout_ms: Optional[int] = None) -> bytes: ...
     def send(self, data: bytes, block: bool = True) -> bool: ...
     def close(self) -> None: ...
+
+
+class PackedBatch(NamedTuple):
+    """What ``recv_packed`` returns: the decoded rows of one batch and the
+    reply routes of THOSE rows, so a reply can never be routed by the
+    state of a later batch."""
+
+    lines: Any        # [B, max_len] u8 tensor
+    lens: Any         # [B] line lengths
+    ids_blob: bytes   # logIDs, concatenated
+    ids_off: Any      # [B + 1] offsets into ids_blob
+    nbytes: int       # wire bytes of the frames
+    #: (conn, rows) per merged chunk, in row order; empty when the
+    #: transport has a single reply channel
+    routes: Tuple[Tuple[Any, int], ...] = ()
+
+    def conn_of(self, row: int):
+        """The conn whose segment holds ``row``; None when there are no
+        routes or ``row`` lies outside every segment. A batch of ONE
+        segment has one sender, so every row (also one past its row
+        count) replies to that conn."""
+        if len(self.routes) == 1:
+            return self.routes[0][0]
+        base = 0
+        for conn, rows in self.routes:
+            if base <= row < base + rows:
+                return conn
+            base += rows
+        return None
 
 
 # ---------------------------------------------------------------------------
@@ -471,6 +500,12 @@ class PairListener:
         self._peers: List[socket.socket] = []
         self._peers_lock = threading.Lock()
         self._last_sender: Optional[socket.socket] = None
+        #: frames a recv()/recv_many() took off the queue but has not
+        #: handed out yet, and each one's conn (always the same length)
+        self._pending: List[bytes] = []
+        self._pending_conns: List[socket.socket] = []
+        #: conn of each frame of the last recv_many batch, for reply(idx)
+        self._batch_conns: List[socket.socket] = []
         self._closed = threading.Event()
         self._ssl_ctx: Optional[ssl.SSLContext] = None
         #: packed fast path (enable_packed): reader threads decode
@@ -615,22 +650,15 @@ class PairListener:
             except OSError:
                 pass
 
-    def _pop_pending(self) -> Optional[bytes]:
-        if getattr(self, "_pending", None):
-            return self._pending.pop(0)
-        return None
-
     def recv(self, timeout_ms: Optional[int] = None) -> bytes:
         if self._closed.is_set():
             raise SocketClosed(self.addr)
-        frame = self._pop_pending()
-        if frame is not None:
-            return frame
+        if self._pending:
+            self._pending_conns.pop(0)  # the two lists stay aligned
+            return self._pending.pop(0)
         try:
-            if timeout_ms is None:
-                conn, frames = self._recv_q.get()
-            else:
-                conn, frames = self._recv_q.get(timeout=timeout_ms / 1000.0)
+            conn, frames = self._recv_q.get(
+                timeout=None if timeout_ms is None else timeout_ms / 1000.0)
         except queue.Empty:
             raise RecvTimeout(self.addr) from None
         self._last_sender = conn
@@ -642,7 +670,7 @@ class PairListener:
         return frames[0]
 
     def has_pending(self) -> bool:
-        return bool(getattr(self, "_pending", None)) or not self._recv_q.empty()
+        return bool(self._pending) or not self._recv_q.empty()
 
     # -- packed fast path ----------------------------------------------
     def enable_packed(self, max_len: int, pin: bool,
@@ -678,12 +706,12 @@ class PairListener:
         return lines, lens, blob, off, nbytes
 
     def recv_packed(self, timeout_ms: int, max_frames: int = 0,
-                    linger_ms: float = 0.0):
+                    linger_ms: float = 0.0) -> PackedBatch:
         """Pop packed chunks, merging up to ``max_frames`` rows within
-        ``linger_ms``: (conn, lines, lens, ids_blob, ids_off, frame_bytes).
-        ``conn`` is the FIRST chunk's sender; per-row routing for merged
-        multi-peer batches is available via ``reply_row`` — each chunk's
-        (conn, row_count) is recorded in ``_batch_conn_segs``."""
+        ``linger_ms``, into one ``PackedBatch``. Its ``routes`` hold one
+        (conn, rows) entry per merged chunk, so ``conn_of(row)`` names
+        each row's sender also when chunks of several peers merged;
+        ``routes[0][0]`` is the first chunk's sender."""
         import torch
 
         try:
@@ -691,15 +719,11 @@ class PairListener:
         except queue.Empty:
             raise RecvTimeout(self.addr) from None
         self._last_sender = conn
-        lines, lens, blob, off, nbytes = self._as_packed(item)
-        if max_frames <= 0 or lines.shape[0] >= max_frames:
-            self._batch_conn_segs = [(conn, int(lines.shape[0]))]
-            return conn, lines, lens, blob, off, nbytes
-        chunks = [(lines, lens, blob, off, nbytes)]
-        segs = [(conn, int(lines.shape[0]))]
-        total = int(lines.shape[0])
+        chunks = [self._as_packed(item)]
+        total = int(chunks[0][0].shape[0])
+        routes = [(conn, total)]
         deadline = time.monotonic() + linger_ms / 1000.0
-        while total < max_frames:
+        while total < max_frames:  # max_frames <= 0: no merging
             remaining = deadline - time.monotonic()
             try:
                 c, item = self._recv_q.get(
@@ -710,11 +734,10 @@ class PairListener:
                 break
             ch = self._as_packed(item)
             chunks.append(ch)
-            segs.append((c, int(ch[0].shape[0])))
+            routes.append((c, int(ch[0].shape[0])))
             total += int(ch[0].shape[0])
-        self._batch_conn_segs = segs
         if len(chunks) == 1:
-            return conn, lines, lens, blob, off, nbytes
+            return PackedBatch(*chunks[0], routes=tuple(routes))
         lines = torch.cat([c[0] for c in chunks])
         lens = torch.cat([c[1] for c in chunks])
         blob = b"".join(c[2] for c in chunks)
@@ -725,7 +748,7 @@ class PairListener:
             base += int(c[3][-1])
         off = torch.cat(offs)
         nbytes = sum(c[4] for c in chunks)
-        return conn, lines, lens, blob, off, nbytes
+        return PackedBatch(lines, lens, blob, off, nbytes, tuple(routes))
 
     def recv_many(
         self, max_frames: int, timeout_ms: int, linger_ms: float = 0.0
@@ -739,88 +762,50 @@ class PairListener:
         every reply to ITS sender even with several concurrent peers
         (the reference's Pair0 was strictly 1:1 and never faced this).
         """
-        out: List[bytes] = list(getattr(self, "_pending", None) or [])
-        conns: List = list(getattr(self, "_pending_conns", None) or [])
-        self._pending = []
-        self._pending_conns = []
-        if len(out) >= max_frames:
-            self._pending = out[max_frames:]
-            self._pending_conns = conns[max_frames:]
-            self._batch_conns = conns[:max_frames]
-            return out[:max_frames]
-        try:
-            if not out:
-                conn, frames = self._recv_q.get(timeout=timeout_ms / 1000.0)
-                self._last_sender = conn
-                out.extend(frames)
-                conns.extend([conn] * len(frames))
-        except queue.Empty:
-            self._batch_conns = conns
-            return out
-        deadline = time.monotonic() + linger_ms / 1000.0
-        while len(out) < max_frames:
-            remaining = deadline - time.monotonic()
-            try:
-                conn, frames = self._recv_q.get(
-                    timeout=max(remaining, 0) if remaining > 0 else None,
-                    block=remaining > 0,
-                )
-            except queue.Empty:
-                break
+        out, conns = self._pending, self._pending_conns
+
+        def take(block: bool, timeout: Optional[float]) -> None:
+            conn, frames = self._recv_q.get(block=block, timeout=timeout)
             self._last_sender = conn
             out.extend(frames)
             conns.extend([conn] * len(frames))
-        if len(out) > max_frames:
-            self._pending = out[max_frames:]
-            self._pending_conns = conns[max_frames:]
-            out = out[:max_frames]
-            conns = conns[:max_frames]
-        self._batch_conns = conns
-        return out
+
+        try:
+            if not out:
+                take(True, timeout_ms / 1000.0)
+            deadline = time.monotonic() + linger_ms / 1000.0
+            while len(out) < max_frames:
+                remaining = deadline - time.monotonic()
+                take(remaining > 0, remaining if remaining > 0 else None)
+        except queue.Empty:
+            pass  # no first frame in time, or the linger ran out
+        # whatever exceeds the batch waits, with its conns, for the next call
+        self._pending, self._pending_conns = out[max_frames:], conns[max_frames:]
+        self._batch_conns = conns[:max_frames]
+        return out[:max_frames]
 
     def reply(self, idx: int, data: bytes) -> bool:
         """Reply to the sender of frame ``idx`` of the last recv_many batch
         (falls back to the last sender when unknown)."""
-        conns = getattr(self, "_batch_conns", None)
-        conn = conns[idx] if conns and 0 <= idx < len(conns) else self._last_sender
-        if conn is None:
-            return False
-        try:
-            if self._ws:
-                conn.sendall(_ws_encode(data, mask=False))
-            else:
-                _send_frame(conn, data, self._sp)
-            return True
-        except OSError:
-            return False
-
-    def reply_row(self, idx: int, data: bytes) -> bool:
-        """Reply to the sender of ROW ``idx`` of the last recv_packed batch
-        (merged multi-peer chunks route per-row via the recorded
-        (conn, row_count) segments; falls back to the last sender)."""
-        conn = None
-        segs = getattr(self, "_batch_conn_segs", None)
-        if segs:
-            base = 0
-            for c, rows in segs:
-                if idx < base + rows:
-                    conn = c
-                    break
-                base += rows
-        return self.reply_conn(conn if conn is not None else self._last_sender,
-                               data)
+        conns = self._batch_conns
+        return self._send_to(
+            conns[idx] if 0 <= idx < len(conns) else self._last_sender, data)
 
     def send(self, data: bytes, block: bool = True) -> bool:
         """Reply to the most recent sender (request/reply fallback mode)."""
         return self.reply_conn(self._last_sender, data)
 
     def reply_conn(self, conn, data: bytes) -> bool:
-        """Reply to a SPECIFIC peer (the packed loop routes each batch's
-        replies to that batch's sender; per-row routing for merged
-        multi-peer chunks is ``reply_row``)."""
+        """Reply to a SPECIFIC peer: the packed loop routes each alert
+        with ``batch.conn_of(row)``. ``conn=None`` (no route known) falls
+        back to the newest peer."""
         if conn is None:
             with self._peers_lock:
                 conn = self._peers[-1] if self._peers else None
+        return self._send_to(conn, data)
+
+    def _send_to(self, conn, data: bytes) -> bool:
+        """The one framed send of the reply path (ws or SP / compact)."""
         if conn is None:
             return False
         try:
@@ -1298,7 +1283,9 @@ class ShmListener:
         return True
 
     def recv_packed(self, timeout_ms: int, max_frames: int = 0,
-                    linger_ms: float = 0.0):
+                    linger_ms: float = 0.0) -> PackedBatch:
+        """One ``PackedBatch`` decoded in place from the ring. ``routes``
+        is empty: ring replies are single-channel (s2c)."""
         if self._closed.is_set():
             raise SocketClosed(self.addr)
         max_len, pin, mf = self._packed or (256, False, 4096)
@@ -1308,7 +1295,7 @@ class ShmListener:
             mf, timeout_ms, max_len, pin)
         if lines.shape[0] == 0:
             raise RecvTimeout(self.addr)
-        return None, lines, lens, blob, off, int(nbytes)
+        return PackedBatch(lines, lens, blob, off, int(nbytes))
 
     def has_pending(self) -> bool:
         return bool(self._pending) or self._c2s.pending() > 0
@@ -1322,10 +1309,6 @@ class ShmListener:
         return self.send(data)
 
     def reply(self, idx: int, data: bytes) -> bool:
-        return self.send(data)
-
-    def reply_row(self, idx: int, data: bytes) -> bool:
-        """Ring replies are single-channel (s2c)."""
         return self.send(data)
 
     def close(self) -> None:

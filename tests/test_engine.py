@@ -401,3 +401,112 @@ def test_reply_indices_survive_empty_frame_filtering(ipc_addr):
     eng.stop()
     # frames at original indices 1 ("x") and 3 ("y") get the replies
     assert sock.replies == [(1, b"out:x"), (3, b"out:y")]
+
+
+class PackedFakeSock:
+    """Fake packed listener: hands out prepared PackedBatches, then times
+    out; has_pending() is always true, so the pipelined loop keeps a
+    batch in flight across the next receive. ``events`` records the
+    order of receives and replies."""
+
+    def __init__(self, batches):
+        self.addr = "inproc://fake-packed"
+        self._batches = list(batches)
+        self.events = []
+
+    def enable_packed(self, max_len, pin, max_frames=4096):
+        return True
+
+    def recv_packed(self, timeout_ms, max_frames=0, linger_ms=0.0):
+        if self._batches:
+            batch = self._batches.pop(0)
+            self.events.append(("recv", batch.ids_blob))
+            return batch
+        time.sleep(0.005)
+        raise RecvTimeout(self.addr)
+
+    def has_pending(self):
+        return True
+
+    def reply_conn(self, conn, data):
+        self.events.append(("reply", conn, data))
+        return True
+
+    def send(self, data, block=True):
+        raise AssertionError("the packed loop replies through reply_conn")
+
+    def close(self):
+        pass
+
+    @property
+    def replies(self):
+        return [e[1:] for e in self.events if e[0] == "reply"]
+
+
+class PipelinedComponent:
+    """submit/collect component: collect returns one alert per row in
+    ``alert_rows``, tagged with the batch it was submitted for."""
+
+    def __init__(self, alert_rows):
+        self.alert_rows = alert_rows
+
+    def process(self, data):
+        return None
+
+    def process_batch(self, frames):
+        return [None] * len(frames)
+
+    def supports_packed_frames(self):
+        return True
+
+    def process_packed_frames(self, lines, lens, blob, off):
+        raise AssertionError("the pipelined API must be used")
+
+    def submit_packed_frames(self, lines, lens, blob, off):
+        return blob  # the token names the batch
+
+    def collect_packed_frames(self, token):
+        return [(row, token + b":%d" % row) for row in self.alert_rows]
+
+
+def _packed_batch(tag, *routes):
+    import torch
+
+    from detectmateservice_amd.engine.sockets import PackedBatch
+
+    rows = sum(n for _, n in routes)
+    return PackedBatch(torch.zeros((rows, 4), dtype=torch.uint8),
+                       torch.zeros(rows, dtype=torch.int32), tag,
+                       torch.zeros(rows + 1, dtype=torch.int64), 10 * rows,
+                       routes)
+
+
+def _run_packed(ipc_addr, sock, component, n_replies):
+    eng = Engine(_settings(ipc_addr, engine_packed_mode=True), component,
+                 socket_factory=RecordingFactory(sock))
+    eng.start()
+    deadline = time.time() + 5.0
+    while len(sock.replies) < n_replies and time.time() < deadline:
+        time.sleep(0.01)
+    eng.stop()
+
+
+def test_pipelined_packed_replies_use_their_own_batch_routes(ipc_addr):
+    """Batch A is still in flight when batch B (another peer) is
+    received; A's alert must go to A's peer and B's to B's."""
+    sock = PackedFakeSock([_packed_batch(b"A", ("peer-A", 2)),
+                           _packed_batch(b"B", ("peer-B", 2))])
+    _run_packed(ipc_addr, sock, PipelinedComponent(alert_rows=(0,)), 2)
+    assert sock.replies == [("peer-A", b"A:0"), ("peer-B", b"B:0")]
+    # the arrangement really is the hazardous one: B was received
+    # before A's reply went out
+    assert sock.events.index(("recv", b"B")) < sock.events.index(
+        ("reply", "peer-A", b"A:0"))
+
+
+def test_pipelined_packed_merged_batch_routes_per_row(ipc_addr):
+    """One batch merged from two peers: each alert row replies to the
+    peer whose segment holds it."""
+    sock = PackedFakeSock([_packed_batch(b"M", ("peer-A", 2), ("peer-B", 2))])
+    _run_packed(ipc_addr, sock, PipelinedComponent(alert_rows=(1, 2)), 2)
+    assert sock.replies == [("peer-A", b"M:1"), ("peer-B", b"M:2")]

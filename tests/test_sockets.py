@@ -395,10 +395,14 @@ def test_recv_packed_merges_chunks(tmp_path):
         got = 0
         ids = []
         while got < 50:
-            conn, lines, lens, blob, off, nbytes = listener.recv_packed(
+            lines, lens, blob, off, nbytes, routes = listener.recv_packed(
                 5000, max_frames=4096, linger_ms=200.0)
             B = int(lines.shape[0])
             assert nbytes > 0
+            # one peer: every merged chunk routes to the same conn, and
+            # the chunks' row counts add up to the batch
+            assert len({c for c, _ in routes}) == 1
+            assert sum(n for _, n in routes) == B
             for i in range(B):
                 text = bytes(lines[i, : int(lens[i])].numpy().tobytes())
                 lid = blob[int(off[i]):int(off[i + 1])].decode()
@@ -496,8 +500,9 @@ def test_shm_packed_recv(monkeypatch):
         assert dialer.send_many(frames, block=True) == 200
         got = 0
         while got < 200:
-            _c, lines, lens, blob, off, nb = listener.recv_packed(
+            lines, lens, blob, off, nb, routes = listener.recv_packed(
                 2000, max_frames=4096)
+            assert routes == ()  # ring replies are single-channel
             for i in range(lines.shape[0]):
                 lid = blob[int(off[i]):int(off[i + 1])].decode()
                 text = bytes(lines[i, : int(lens[i])].numpy().tobytes()).decode()
@@ -629,8 +634,9 @@ def test_reply_routes_to_right_peer_with_interleaved_recv_styles(tmp_path):
 
 
 def test_reply_row_merged_multi_peer_packed(tmp_path):
-    """recv_packed merging chunks from TWO peers records per-chunk conn
-    segments; reply_row routes each row's reply to ITS sender."""
+    """recv_packed merging chunks from TWO peers returns per-chunk
+    (conn, rows) routes; reply_conn(batch.conn_of(row)) sends each row's
+    reply to ITS sender."""
     from detectmateservice_amd import ops
     from detectmateservice_amd.schemas import LogSchema
 
@@ -648,29 +654,89 @@ def test_reply_row_merged_multi_peer_packed(tmp_path):
         assert da.send_many(fa, block=True) == 5
         time.sleep(0.3)  # let A's chunk land first
         assert db.send_many(fb, block=True) == 5
-        total, rows = 0, []
+        total, where = 0, {}  # logID -> (its batch, its row in that batch)
         while total < 10:
-            _c, lines, lens, blob, off, nb = listener.recv_packed(
+            batch = listener.recv_packed(
                 5000, max_frames=4096, linger_ms=400.0)
-            B = int(lines.shape[0])
+            B = int(batch.lines.shape[0])
+            off, blob = batch.ids_off, batch.ids_blob
             for i in range(B):
-                rows.append(blob[int(off[i]):int(off[i + 1])].decode())
-            # reply to the first row of this merged batch per peer group
+                where[blob[int(off[i]):int(off[i + 1])].decode()] = (batch, i)
             total += B
-        assert sorted(rows) == sorted([f"a{i}" for i in range(5)] + [f"b{i}" for i in range(5)])
-        # the last recv_packed call merged at least A's and B's chunks when
-        # both arrived; route one reply to each side using reply_row on the
-        # row indices we saw
-        idx_a = rows.index("a0")
-        idx_b = rows.index("b0")
-        assert listener.reply_row(idx_a, b"ra")
-        assert listener.reply_row(idx_b, b"rb")
+        assert sorted(where) == sorted([f"a{i}" for i in range(5)] + [f"b{i}" for i in range(5)])
+        # both chunks were sent before the first recv_packed call, which
+        # lingers 0.4 s, so one call merged them; route one reply to each
+        # side through the routes of the batch that holds the row
+        batch_a, idx_a = where["a0"]
+        batch_b, idx_b = where["b0"]
+        assert batch_a is batch_b and len(batch_a.routes) >= 2
+        assert listener.reply_conn(batch_a.conn_of(idx_a), b"ra")
+        assert listener.reply_conn(batch_b.conn_of(idx_b), b"rb")
         assert da.recv(timeout_ms=3000) == b"ra"
         assert db.recv(timeout_ms=3000) == b"rb"
     finally:
         da.close()
         db.close()
         listener.close()
+
+
+def test_packed_batch_conn_of():
+    """The one prefix-sum walk over (conn, rows) routes."""
+    from detectmateservice_amd.engine.sockets import PackedBatch
+
+    def batch(*routes):
+        return PackedBatch(None, None, b"", None, 0, routes)
+
+    two = batch(("A", 3), ("B", 2))
+    assert [two.conn_of(r) for r in (0, 2)] == ["A", "A"]
+    assert [two.conn_of(r) for r in (3, 4)] == ["B", "B"]
+    assert two.conn_of(5) is None and two.conn_of(-1) is None
+    assert batch().conn_of(0) is None
+    # one segment = one sender: every row replies to it
+    assert batch(("A", 3)).conn_of(7) == "A"
+
+
+def test_recv_keeps_pending_conns_aligned(tmp_path):
+    """recv() taking frames out of the pending list must take their conns
+    too, or a later recv_many pairs the next peer's frame with a stale
+    conn and reply(idx) goes to the wrong sender."""
+    addr = f"ipc://{tmp_path}/align.ipc"
+    listener = PairListener(addr)
+    da = PairDialer(addr)
+    db = PairDialer(addr)
+    try:
+        assert da.wait_connected(5.0) and db.wait_connected(5.0)
+        assert da.send_many([b"a1", b"a2", b"a3"], block=True) == 3
+        assert listener.recv(timeout_ms=3000) == b"a1"
+        assert listener.recv(timeout_ms=3000) == b"a2"  # from pending
+        assert db.send(b"b1")
+        # a3 is pending; the linger ends as soon as b1 makes two frames
+        batch = listener.recv_many(2, 3000, linger_ms=3000.0)
+        assert batch == [b"a3", b"b1"]
+        assert listener.reply(0, b"for-a")
+        assert listener.reply(1, b"for-b")
+        assert da.recv(timeout_ms=3000) == b"for-a"
+        assert db.recv(timeout_ms=3000) == b"for-b"
+    finally:
+        da.close()
+        db.close()
+        listener.close()
+
+
+def test_listener_reply_state_is_not_probed():
+    """Reply routing travels with the batch (PackedBatch.routes) and the
+    listener's frame-path state exists from __init__: the hidden
+    'last batch' attributes and their getattr probes stay removed."""
+    from pathlib import Path
+
+    import detectmateservice_amd.engine as engine_pkg
+
+    root = Path(engine_pkg.__file__).parent
+    assert "_batch_conn" not in (root / "engine.py").read_text()
+    sockets_src = (root / "sockets.py").read_text()
+    for needle in ('getattr(self, "_pending', 'getattr(self, "_batch_conn',
+                   "_batch_conn_segs"):
+        assert needle not in sockets_src, needle
 
 
 def test_shm_listener_drops_stale_ring_from_crashed_run(monkeypatch):
