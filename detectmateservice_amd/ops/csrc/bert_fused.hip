@@ -30,6 +30,18 @@
 //   schedule and ends in pool_embed instead: the pooled vector and / or its
 //   distance from a fitted diagonal Gaussian.
 //
+// Operand feed (profiles/r19_operand_pipeline.txt). The kernel is bound by
+// operand latency, not by MFMA, L2 or LDS throughput, so the GEMMs make the
+// weight stream explicit: a quad's K/32 weight fragments and its bias are
+// all issued before its first MFMA (quad_operands) and the chain steps down
+// through counted vmcnt waits; the next quad's are issued between the K
+// chain and the epilogue; and the barrier in front of every GEMM is executed
+// inside block_gemm, after the first quad's loads have been issued, so they
+// are in flight while the wave waits for the block (a `|` below directly in
+// front of a GEMM is that barrier). The A side stays as the compiler
+// schedules it: double-buffering the ds_read_b128 by K step was built and
+// measured no gain on top of this.
+//
 // Operand order. The 16x16x32 bf16 A and B fragment layouts are the same
 // function of the lane (row or column lane&15, k (lane>>4)*8..+7), so
 // mfma(weight, activation) yields the transposed tile of mfma(activation,
@@ -180,21 +192,20 @@ static __device__ __forceinline__ short4v pack_bf16x4(f32x4 v) {
 // tiles, or merely read through lds_frag, the qkv GEMM comes out between
 // 719 and 806 instructions instead of 741 and spills up to 13 more
 // registers (profiles/r15_fused_refactor_isa.txt).
-template <int K, int MODE, int ACT, int WTS, int ABL, bool BIAS, bool SWAP>
-static __device__ __forceinline__ void gemm_quad(
-    const lds_short* __restrict__ in_lds, int in_stride,
+// One quad is three steps, so that gemm_quads can place the next quad's
+// loads between this quad's K chain and its epilogue.
+//
+// quad_operands: every weight fragment of quad fn (K/32 global_load_dwordx4,
+// 4 VGPRs each) and its bias, all issued back to back. Nothing here touches
+// LDS, so it may run ahead of the barrier that guards in_lds.
+template <int K, int WTS, int ABL, bool BIAS, bool SWAP>
+static __device__ __forceinline__ void quad_operands(
     const glob_cshort* __restrict__ Wt, const glob_cfloat* __restrict__ bias,
-    lds_short* __restrict__ out_lds, int out_stride,
-    lds_short* __restrict__ x_lds, lds_short* __restrict__ vt_lds, int fn,
-    int lane, bf16x8 zb) {
-  static_assert(SWAP || MODE == 1, "only the V quads keep weight-as-B order");
-  constexpr int KS = K / 32;
-  const int l15 = lane & 15;
-  const int l4 = lane >> 4;
+    int fn, int l15, int l4, bf16x8 zb, bf16x8 (&w)[K / 32], f32x4& binit) {
   // bias up front: a bias load in the epilogue made the compiler wait
   // vmcnt(0) mid-GEMM, draining the weight-load pipeline with it. It seeds
   // the accumulators, which adds it in f32 at no instruction at all.
-  f32x4 binit = {0.f, 0.f, 0.f, 0.f};
+  binit = {0.f, 0.f, 0.f, 0.f};
   if constexpr (BIAS) {
     if constexpr (SWAP) {
       binit = *(const __attribute__((address_space(1))) f32x4*)(bias + fn * 16 +
@@ -204,18 +215,30 @@ static __device__ __forceinline__ void gemm_quad(
       binit = {bval, bval, bval, bval};
     }
   }
-  f32x4 acc[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = binit;
-#pragma unroll 4
-  for (int ks = 0; ks < KS; ++ks) {
-    bf16x8 w;
+  for (int ks = 0; ks < K / 32; ++ks) {
     if constexpr (ABL & 1) {
-      w = zb;
+      w[ks] = zb;
     } else {
-      w = *(const __attribute__((address_space(1))) bf16x8*)(
+      w[ks] = *(const __attribute__((address_space(1))) bf16x8*)(
           Wt + (long)(fn * 16 + l15) * WTS + ks * 32 + l4 * 8);
     }
+  }
+  // Left alone, the scheduler sinks each load to just before the MFMA that
+  // needs it and the chain waits a full L2 round trip per K step.
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// quad_chain: the four K chains of a quad, ascending k, each accumulator
+// seeded by the caller. The A-fragment reads are left to the compiler's
+// scheduler (an explicit K-step double buffer, 32 VGPRs, measured no gain).
+template <int K, int ABL, bool SWAP>
+static __device__ __forceinline__ void quad_chain(
+    const lds_short* __restrict__ in_lds, int in_stride, int l15, int l4,
+    bf16x8 zb, const bf16x8 (&w)[K / 32], f32x4 (&acc)[4]) {
+  constexpr int KS = K / 32;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
     for (int fm = 0; fm < 4; ++fm) {
       bf16x8 a;
@@ -226,11 +249,20 @@ static __device__ __forceinline__ void gemm_quad(
             in_lds + (fm * 16 + l15) * in_stride + ks * 32 + l4 * 8);
       }
       if constexpr (SWAP)
-        acc[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, acc[fm], 0, 0, 0);
+        acc[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[ks], a, acc[fm], 0, 0, 0);
       else
-        acc[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w, acc[fm], 0, 0, 0);
+        acc[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w[ks], acc[fm], 0, 0, 0);
     }
   }
+}
+
+// quad_store: the epilogue of quad fn.
+template <int MODE, int ACT, bool SWAP>
+static __device__ __forceinline__ void quad_store(
+    lds_short* __restrict__ out_lds, int out_stride,
+    lds_short* __restrict__ x_lds, lds_short* __restrict__ vt_lds, int fn,
+    int l15, int l4, const f32x4 (&acc)[4]) {
+  static_assert(SWAP || MODE == 1, "only the V quads keep weight-as-B order");
 #pragma unroll
   for (int fm = 0; fm < 4; ++fm) {
     f32x4 v = acc[fm];
@@ -261,32 +293,70 @@ static __device__ __forceinline__ void gemm_quad(
   }
 }
 
-// CNT consecutive quads from fn0, all in one operand order. unroll 2: the
-// second quad's (independent) weight loads issue under the first quad's
-// MFMA chains, hiding the L2 latency that dominates the per-quad cost
+// CNT consecutive quads from fn0, all in one operand order. One quad body
+// at a time: all of a quad's weight fragments are in flight before its
+// first MFMA, and the next quad's are issued between this quad's K chain
+// and its epilogue, into the registers the chain has just freed, so their
+// L2 latency runs under the epilogue.
+//
+// BAR: this call executes the block barrier that guards in_lds (block_gemm).
+// The first quad's loads are in flight when the wave arrives at it, so the
+// phase no longer opens with a bare L2 round trip on all eight waves. Each
+// recorder in `rec` (none, or the timed variant's) stamps "barrier crossed".
 template <int K, int MODE, int ACT, int WTS, int ABL, bool BIAS, bool SWAP,
-          int CNT>
+          int CNT, bool BAR, typename... REC>
 static __device__ __forceinline__ void gemm_quads(
     const lds_short* __restrict__ in_lds, int in_stride,
     const glob_cshort* __restrict__ Wt, const glob_cfloat* __restrict__ bias,
     lds_short* __restrict__ out_lds, int out_stride,
     lds_short* __restrict__ x_lds, lds_short* __restrict__ vt_lds, int fn0,
-    int lane, bf16x8 zb) {
-#pragma unroll 2
-  for (int q = 0; q < CNT; ++q)
-    gemm_quad<K, MODE, ACT, WTS, ABL, BIAS, SWAP>(in_lds, in_stride, Wt, bias, out_lds,
-                                            out_stride, x_lds, vt_lds, fn0 + q,
-                                            lane, zb);
+    int lane, bf16x8 zb, REC&... rec) {
+  const int l15 = lane & 15;
+  const int l4 = lane >> 4;
+  bf16x8 w[K / 32];
+  f32x4 binit;
+  quad_operands<K, WTS, ABL, BIAS, SWAP>(Wt, bias, fn0, l15, l4, zb, w, binit);
+  // The timed variant reads the clock right behind the barrier and waits
+  // for it there (an outstanding scalar load turns every counted lgkmcnt wait
+  // of the chain into lgkmcnt(0)), but files the stamp after the last quad:
+  // the recorder lives in scratch, and a store in here would sit on vmcnt.
+  unsigned long long crossed = 0;
+  if constexpr (BAR) {
+    // lowers to s_waitcnt lgkmcnt(0); s_barrier: the loads stay in flight
+    __syncthreads();
+    if constexpr (sizeof...(REC) != 0) {
+      crossed = __builtin_amdgcn_s_memrealtime();
+      asm volatile("" : "+s"(crossed));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int q = 0; q < CNT; ++q) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = binit;
+    quad_chain<K, ABL, SWAP>(in_lds, in_stride, l15, l4, zb, w, acc);
+    if (q + 1 < CNT)
+      quad_operands<K, WTS, ABL, BIAS, SWAP>(Wt, bias, fn0 + q + 1, l15, l4,
+                                             zb, w, binit);
+    quad_store<MODE, ACT, SWAP>(out_lds, out_stride, x_lds, vt_lds, fn0 + q,
+                                l15, l4, acc);
+  }
+  if constexpr (BAR) (rec.mark_at(crossed), ...);
 }
 
+// BAR: the block barrier that precedes this GEMM is executed inside it,
+// after the wave's first weight and bias loads have been issued and before
+// anything touches in_lds; the caller then leaves its own __syncthreads()
+// out. Every wave executes exactly one barrier on every path.
 template <int K, int N, int MODE, int ACT, int WTS, int ABL = 0,
-          bool BIAS = true>
+          bool BIAS = true, bool BAR = false, typename... REC>
 static __device__ __attribute__((noinline)) void block_gemm(
     const lds_short* __restrict__ in_lds, int in_stride,
     const glob_cshort* __restrict__ Wt, const glob_cfloat* __restrict__ bias,
     lds_short* __restrict__ out_lds, int out_stride,
     lds_short* __restrict__ x_lds, lds_short* __restrict__ vt_lds, int wid,
-    int lane) {
+    int lane, REC&... rec) {
   bf16x8 zb;
   if constexpr (ABL != 0) {
 #pragma unroll
@@ -304,33 +374,33 @@ static __device__ __attribute__((noinline)) void block_gemm(
   constexpr int QPW = FPW / 4;  // quads per wave
   const int fn_lo = __builtin_amdgcn_readfirstlane(wid) * QPW;
   if constexpr (MODE != 1) {
-    gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, QPW>(in_lds, in_stride, Wt, bias,
-                                                  out_lds, out_stride, x_lds,
-                                                  vt_lds, fn_lo, lane, zb);
+    gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, QPW, BAR>(
+        in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds, fn_lo,
+        lane, zb, rec...);
   } else {
     // qkv: fn below FN_SWAP (Q|K, row-major) runs operand-swapped, the V
     // columns in weight-as-B order. The choice is made ONCE per wave on a
     // scalar, outside the MFMA loops, and every arm has compile-time trip
     // counts (a per-quad `n < 2H` test compiled to a divergent exec-mask
-    // ladder of ~200 scalar instructions around the MFMAs; runtime trip
-    // counts lose the unroll-2 weight prefetch). With QPW = 3 wave 5 owns
-    // fn 15 (K) and 16, 17 (V): the one mixed wave.
+    // ladder of ~200 scalar instructions around the MFMAs). With QPW = 3
+    // wave 5 owns fn 15 (K) and 16, 17 (V): the one mixed wave. Its second
+    // run of quads starts without a prefetch under the first run's epilogue:
+    // the shallower schedule, on one wave of eight.
     constexpr int FN_SWAP = 2 * BF_H / 16;
     constexpr int NSW = FN_SWAP % QPW;  // swapped quads of the mixed wave
     if (fn_lo + QPW <= FN_SWAP) {
-      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, QPW>(in_lds, in_stride, Wt, bias,
-                                                    out_lds, out_stride, x_lds,
-                                                    vt_lds, fn_lo, lane, zb);
+      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, QPW, BAR>(
+          in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds,
+          fn_lo, lane, zb, rec...);
     } else if (fn_lo >= FN_SWAP) {
-      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, false, QPW>(in_lds, in_stride, Wt,
-                                                     bias, out_lds, out_stride,
-                                                     x_lds, vt_lds, fn_lo, lane,
-                                                     zb);
+      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, false, QPW, BAR>(
+          in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds,
+          fn_lo, lane, zb, rec...);
     } else {
-      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, NSW>(in_lds, in_stride, Wt, bias,
-                                                    out_lds, out_stride, x_lds,
-                                                    vt_lds, fn_lo, lane, zb);
-      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, false, QPW - NSW>(
+      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, true, NSW, BAR>(
+          in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds,
+          fn_lo, lane, zb, rec...);
+      gemm_quads<K, MODE, ACT, WTS, ABL, BIAS, false, QPW - NSW, false>(
           in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds,
           fn_lo + NSW, lane, zb);
     }
@@ -565,8 +635,10 @@ template <>
 struct StampRecorder<true> {
   unsigned long long t[BF_NSTAMP];
   int n = 0;
-  __device__ void mark() {
-    if (n < BF_NSTAMP) t[n++] = __builtin_amdgcn_s_memrealtime();
+  __device__ void mark() { mark_at(__builtin_amdgcn_s_memrealtime()); }
+  // a clock value read earlier; slots are still filed in schedule order
+  __device__ void mark_at(unsigned long long now) {
+    if (n < BF_NSTAMP) t[n++] = now;
   }
   // out: [B, BF_WAVES, BF_NSTAMP]
   __device__ void flush(unsigned long long* out, int line, int wid, int lane) {
@@ -577,11 +649,38 @@ struct StampRecorder<true> {
   }
 };
 
-// The schedule: phase, stamp, barrier, stamp. Stamp slots: 0 kernel start,
-// 1-2 embed, then per layer (work done, barrier crossed) for qkv,
-// attention, proj+LN1 and ffn+LN2, and one final stamp. HEAD picks the tail
-// phase; with HEAD_EMBED `scores` is unused, with HEAD_SCORE the four
-// arguments after `stamps_out` are.
+// A block_gemm that executes the barrier in front of it (BAR). Where that
+// barrier carries a "barrier crossed" stamp the timed variant hands its
+// recorder in; every other kernel calls the recorder-free instance, so the
+// production kernel and the timed one run the same GEMM code but for the
+// stamp. STAMPED is false for the barriers inside the FFN, which have no
+// stamp slots.
+template <int K, int N, int MODE, int ACT, int WTS, int ABL, bool BIAS,
+          bool STAMPED, bool TIMED>
+static __device__ __forceinline__ void block_gemm_bar(
+    const lds_short* __restrict__ in_lds, int in_stride,
+    const glob_cshort* __restrict__ Wt, const glob_cfloat* __restrict__ bias,
+    lds_short* __restrict__ out_lds, int out_stride,
+    lds_short* __restrict__ x_lds, lds_short* __restrict__ vt_lds, int wid,
+    int lane, StampRecorder<TIMED>& stamp) {
+  if constexpr (STAMPED && TIMED)
+    block_gemm<K, N, MODE, ACT, WTS, ABL, BIAS, true>(
+        in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds, wid,
+        lane, stamp);
+  else
+    block_gemm<K, N, MODE, ACT, WTS, ABL, BIAS, true>(
+        in_lds, in_stride, Wt, bias, out_lds, out_stride, x_lds, vt_lds, wid,
+        lane);
+}
+
+// The schedule: phase, stamp, barrier, stamp. The barrier in front of a GEMM
+// is executed inside it (block_gemm BAR), together with its "barrier
+// crossed" stamp; where a probe variant leaves the GEMM out, the barrier and
+// the stamp stand in its place. Stamp slots: 0 kernel start, 1-2 embed, then
+// per layer (work done, barrier crossed) for qkv, attention, proj+LN1 and
+// ffn+LN2, and one final stamp. HEAD picks the tail phase; with HEAD_EMBED
+// `scores` is unused, with HEAD_SCORE the four arguments after `stamps_out`
+// are.
 template <int PHASES, bool TIMED = false, int ABL = 0, int HEAD = HEAD_SCORE>
 static __device__ __forceinline__ void bert_fused_body(
     const unsigned char* __restrict__ lines,  // [B, max_len]
@@ -608,68 +707,85 @@ static __device__ __forceinline__ void bert_fused_body(
   stamp.mark();
   embed(lines, start, end, wb, x, line, max_len, tid);
   stamp.mark();
-  __syncthreads();
-  stamp.mark();
 
   for (int layer = 0; layer < n_layers; ++layer) {
     const short* lw = wb + WB_LAYER0 + (long)layer * LW_SIZE;
     const float* lf = fb + (long)layer * FB_SIZE;
 
-    if (PHASES & PH_QKV)
-      block_gemm<BF_H, 3 * BF_H, 1, 0, BF_H, ABL>(x, XS, (glob_cshort*)(lw + LW_QKV),
-                                             (glob_cfloat*)(lf + FB_BQKV), QkTile::ptr(), QKS, x, VtTile::ptr(),
-                                             wid, lane);
+    // opens with the barrier that ends embed or the previous layer's LN2
+    if (PHASES & PH_QKV) {
+      block_gemm_bar<BF_H, 3 * BF_H, 1, 0, BF_H, ABL, true, true, TIMED>(
+          x, XS, (glob_cshort*)(lw + LW_QKV), (glob_cfloat*)(lf + FB_BQKV),
+          QkTile::ptr(), QKS, x, VtTile::ptr(), wid, lane, stamp);
+    } else {
+      __syncthreads();
+      stamp.mark();
+    }
     stamp.mark();
     __syncthreads();
     stamp.mark();
 
     if (PHASES & PH_ATTN) attention(wid, lane);
     stamp.mark();
-    __syncthreads();
-    stamp.mark();
 
-    // x += Wo(attn); LN1
-    if (PHASES & PH_PROJ)
-      block_gemm<BF_H, BF_H, 2, 0, BF_H, ABL>(AttnOut::ptr(), XS, (glob_cshort*)(lw + LW_WO),
-                                         (glob_cfloat*)(lf + FB_BO), nullptr, 0, x,
-                                         nullptr, wid, lane);
+    // | x += Wo(attn) | LN1
+    if (PHASES & PH_PROJ) {
+      block_gemm_bar<BF_H, BF_H, 2, 0, BF_H, ABL, true, true, TIMED>(
+          AttnOut::ptr(), XS, (glob_cshort*)(lw + LW_WO),
+          (glob_cfloat*)(lf + FB_BO), nullptr, 0, x, nullptr, wid, lane, stamp);
+    } else {
+      __syncthreads();
+      stamp.mark();
+    }
     __syncthreads();
     if (PHASES & PH_LN)
       block_layernorm(x, lw + LW_LN1G, lw + LW_LN1B, wid, lane, eps);
     stamp.mark();
-    __syncthreads();
-    stamp.mark();
 
     // FFN in two K=256 halves, both reading the LN1 output in x:
-    // buf = gelu(x @ W1_0); XMid = x + buf @ W2_0 + b2;
-    // buf = gelu(x @ W1_1); x = XMid + buf @ W2_1; LN2
-    if (PHASES & PH_FFN)
+    // | buf = gelu(x @ W1_0) | XMid = x + buf @ W2_0 + b2
+    // | buf = gelu(x @ W1_1) | x = XMid + buf @ W2_1 | LN2
+    // The first of the five barriers is the one after LN1 and has the stamp.
+    if (PHASES & PH_FFN) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      block_gemm<BF_H, BF_FFN / 2, 0, 1, BF_H, ABL>(
-          x, XS, (glob_cshort*)(lw + LW_W1 + (long)h * (BF_FFN / 2) * BF_H),
-          (glob_cfloat*)(lf + FB_B1 + h * (BF_FFN / 2)), FfnHalf::ptr(), QKS, nullptr,
-          nullptr, wid, lane);
+      for (int h = 0; h < 2; ++h) {
+        const glob_cshort* w1 =
+            (glob_cshort*)(lw + LW_W1 + (long)h * (BF_FFN / 2) * BF_H);
+        const glob_cfloat* b1 = (glob_cfloat*)(lf + FB_B1 + h * (BF_FFN / 2));
+        // bias b2 added once (half 0); half 1 adds only the partial product
+        // (compile-time: a runtime null test on the pointer, a VGPR in the
+        // noinline callee, put an exec-mask branch in front of every quad)
+        if (h == 0) {
+          block_gemm_bar<BF_H, BF_FFN / 2, 0, 1, BF_H, ABL, true, true, TIMED>(
+              x, XS, w1, b1, FfnHalf::ptr(), QKS, nullptr, nullptr, wid, lane,
+              stamp);
+          block_gemm_bar<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, true, false,
+                         TIMED>(FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2),
+                                (glob_cfloat*)(lf + FB_B2), XMid::ptr(), XS, x,
+                                nullptr, wid, lane, stamp);
+        } else {
+          block_gemm_bar<BF_H, BF_FFN / 2, 0, 1, BF_H, ABL, true, false, TIMED>(
+              x, XS, w1, b1, FfnHalf::ptr(), QKS, nullptr, nullptr, wid, lane,
+              stamp);
+          block_gemm_bar<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, false, false,
+                         TIMED>(
+              FfnHalf::ptr(), QKS,
+              (glob_cshort*)(lw + LW_W2 + (long)h * (BF_FFN / 2)), nullptr, x,
+              XS, XMid::ptr(), nullptr, wid, lane, stamp);
+        }
+      }
       __syncthreads();
-      // bias b2 added once (half 0); half 1 adds only the partial product
-      // (compile-time: a runtime null test on the pointer, a VGPR in the
-      // noinline callee, put an exec-mask branch in front of every quad)
-      if (h == 0)
-        block_gemm<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, true>(
-            FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2), (glob_cfloat*)(lf + FB_B2),
-            XMid::ptr(), XS, x, nullptr, wid, lane);
-      else
-        block_gemm<BF_FFN / 2, BF_H, 3, 0, BF_FFN, ABL, false>(
-            FfnHalf::ptr(), QKS, (glob_cshort*)(lw + LW_W2 + (long)h * (BF_FFN / 2)),
-            nullptr, x, XS, XMid::ptr(), nullptr, wid, lane);
+    } else {
       __syncthreads();
+      stamp.mark();
     }
     if (PHASES & PH_LN)
       block_layernorm(x, lw + LW_LN2G, lw + LW_LN2B, wid, lane, eps);
     stamp.mark();
-    __syncthreads();
-    stamp.mark();
   }
+  // the barrier that ends embed (no layers) or the last layer's LN2
+  __syncthreads();
+  stamp.mark();
 
   if constexpr (HEAD == HEAD_EMBED)
     pool_embed(emb, mu, inv_var, dist, line, tid);
